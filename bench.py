@@ -15,11 +15,20 @@ contiguous bands instead); for N > 1 one RCCL all-gather of the HDR
 accumulator per frame, then every rank repacks the RGBA8 frame from it
 (spt_pack_pixels_async).  Frames are pipelined: frame
 i+1 renders while frame i is gathered (double-buffered frame, second stream).
-After the timed steps, rank 0's assembled frame is checked bit for bit
-against one GPU rendering the whole frame ("frame_check").  Rays = Intersect +
-IntersectP calls, counted by the kernel itself.
+Rays = Intersect + IntersectP calls, counted by the kernel
+itself in one counted frame between the warm-up and the timed steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--no-whitted]
+A plain run sets up, warms up, times the steps, writes the last timed step's
+outputs if --dump-outputs is given, and prints the result line.  --full adds
+everything else after the timed steps: the steps again with the reference's
+blocking pixel read ("ms_per_frame_with_readback"), the PMC digest's figures
+in "roofline" / "valu", at N > 1 the bit-for-bit check of rank 0's assembled
+frame against one GPU rendering the whole frame ("frame_check"), the side
+lines (configs[0..4], Whitted, queue tracer, drop-in) and the CPU baselines;
+--no-cpu, --no-whitted and --no-cornell-extra trim a --full run.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu] [--no-whitted] [--no-cornell-extra]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 import argparse
@@ -72,11 +81,16 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-whitted", action="store_true", help="skip the side lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the read-back steps, the side lines and the CPU "
+                         "baselines, and (N > 1) check the assembled frame against one GPU's")
+    ap.add_argument("--no-cpu", action="store_true", help="(with --full) skip the CPU baseline leg")
+    ap.add_argument("--no-whitted", action="store_true", help="(with --full) skip the side lines")
     ap.add_argument("--no-cornell-extra", action="store_true",
-                    help="skip the configs[2] / configs[3] lines (other launches of the headline kernel: "
-                         "profiling runs keep its per-launch statistics to the headline frame)")
+                    help="(with --full) skip the configs[2] / configs[3] lines (other launches of the headline "
+                         "kernel: profiling runs keep its per-launch statistics to the headline frame)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU sample length")
     return ap.parse_args()
 
@@ -605,6 +619,26 @@ def list_tiled_line(dev, rank, world, distributed, s, sc, cm, spp, workload, fra
     return out
 
 
+SEED_SAMPLE = 1 << 18          # --dump-outputs: entries of the RNG state written
+
+
+def dump_outputs(path, colors, pixels, seeds):
+    """--dump-outputs: the arrays a caller of the timed path receives from its
+    last step -- colors.npy, the HDR accumulator (float32[H, W, 3], every
+    value); pixels.npy, the RGBA8 frame (the four bytes of every packed pixel
+    as float32[H, W, 4]); seeds.npy (one GPU only: at N > 1 a rank holds the
+    RNG state of its own rows alone), SEED_SAMPLE entries of the uint32[2*W*H]
+    RNG state as float64 (exact), at indices drawn once from a fixed seed."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "colors.npy"), colors.cpu().numpy().reshape(H, W, 3))
+    px = pixels.cpu().numpy().view(np.uint8).reshape(H, W, 4)
+    np.save(os.path.join(path, "pixels.npy"), px.astype(np.float32))
+    if seeds is not None:
+        sd = seeds.cpu().numpy().view(np.uint32)
+        idx = np.sort(np.random.RandomState(195).choice(sd.size, SEED_SAMPLE, replace=False))
+        np.save(os.path.join(path, "seeds.npy"), sd[idx].astype(np.float64))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -753,29 +787,36 @@ def main():
         elapsed, kern_ms = t.tolist()
     ms_per_step = elapsed * 1e3 / args.steps
 
-    # The reference's frame ends in a blocking read of the pixels
-    # (smallptGPU.cpp:760 ReadKernelBuffer after every pass): the same steps
-    # again, each followed by a blocking D2H of the (assembled) RGBA8 frame
-    # into page-locked host memory.  Reported beside ms_per_step (which keeps
-    # the device-resident frame the driver's metric times).
-    host_px = torch.empty(W * H, dtype=torch.int32, pin_memory=True)
-    if distributed:
-        dist.barrier()
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-        torch.cuda.synchronize(dev)                  # render (+ gather and repack on gs)
-        host_px.copy_(pixels[(nframe[0] - 1) % nbuf], non_blocking=True)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's frame (assembled on every rank at N > 1)
+        last = (nframe[0] - 1) % nbuf
+        dump_outputs(args.dump_outputs, colors[last], pixels[last], seeds if world == 1 else None)
+
+    ms_readback = None
+    if args.full:
+        # The reference's frame ends in a blocking read of the pixels
+        # (smallptGPU.cpp:760 ReadKernelBuffer after every pass): the same steps
+        # again, each followed by a blocking D2H of the (assembled) RGBA8 frame
+        # into page-locked host memory.  Reported beside ms_per_step (which keeps
+        # the device-resident frame the driver's metric times).
+        host_px = torch.empty(W * H, dtype=torch.int32, pin_memory=True)
+        if distributed:
+            dist.barrier()
         torch.cuda.synchronize(dev)
-    if distributed:
-        dist.barrier()
-    rb = time.perf_counter() - t0
-    if distributed:
-        t = torch.tensor([rb], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        rb = t.item()
-    ms_readback = rb * 1e3 / args.steps
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+            torch.cuda.synchronize(dev)                  # render (+ gather and repack on gs)
+            host_px.copy_(pixels[(nframe[0] - 1) % nbuf], non_blocking=True)
+            torch.cuda.synchronize(dev)
+        if distributed:
+            dist.barrier()
+        rb = time.perf_counter() - t0
+        if distributed:
+            t = torch.tensor([rb], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            rb = t.item()
+        ms_readback = rb * 1e3 / args.steps
 
     # Roofline: algorithmic HBM bytes of one launch =
     # 32 B per pixel of the band (seeds 8 in + 8 out, colour 12 out, pixel 4
@@ -784,7 +825,7 @@ def main():
     launch_bytes = 32 * B * W + 44 * ns
     achieved = launch_bytes / (kern_ms * 1e-3) / 1e9
     flops = 20.0 * counts[2] / world
-    pmc, pmc_src = pmc_digest(BENCH_KERNEL) if world == 1 else (None, None)
+    pmc, pmc_src = pmc_digest(BENCH_KERNEL) if world == 1 and args.full else (None, None)
     out = {
         "metric": "Mrays/sec + ms/frame @1920x1080 Cornell-64spp, 1/2/4/8 GPU; % HBM roofline",
         "value": round(rays_per_frame / (ms_per_step * 1e-3) / 1e6, 2),
@@ -792,6 +833,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(ms_per_step, 3),
         "higher_is_better": True,
         "scaling": "strong",
@@ -804,10 +846,6 @@ def main():
                        "interleaved 8-row groups" if interleaved else "row bands", world, collective_name(),
                        " (pipelined)" if pipelined else "")) if world > 1 else "single GPU"},
         "frames_per_s": round(1e3 / ms_per_step, 3),
-        "ms_per_frame_with_readback": round(ms_readback, 3),
-        "readback_note": "the same step followed by a blocking D2H of the %dx%d RGBA8 frame (%.1f MB) into "
-                         "pinned host memory, as smallptGPU.cpp:760 reads after every pass; max over ranks" % (
-                             W, H, W * H * 4 / 1e6),
         "Msamples_per_s": round(W * H * SPP / (ms_per_step * 1e-3) / 1e6, 2),
         "rays_per_frame": rays_per_frame,
         "kernel_ms": round(kern_ms, 4),
@@ -841,6 +879,12 @@ def main():
                         "note": "render_ms / gather_ms: mean over the timed steps of HIP events around the render "
                                 "launch (render stream) and the HDR all-gather + RGBA8 repack (gather stream); "
                                 "overlap = (max render + max gather - ms_per_step) / max gather"}
+    if args.full:
+        out["ms_per_frame_with_readback"] = round(ms_readback, 3)
+        out["readback_note"] = ("the same step followed by a blocking D2H of the %dx%d RGBA8 frame (%.1f MB) into "
+                                "pinned host memory, as smallptGPU.cpp:760 reads after every pass; max over ranks" % (
+                                    W, H, W * H * 4 / 1e6))
+    if distributed and args.full:
         # Self-check of the sharded path (outside the timed region): the last
         # assembled frame must equal one GPU rendering the whole frame.
         last = (nframe[0] - 1) % nbuf
@@ -855,9 +899,10 @@ def main():
                                and torch.equal(ref_p, pixels[last]))], dtype=torch.int32, device=dev)
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         out["frame_check"] = "assembled frame == single-GPU frame (bit-exact)" if ok.item() else "MISMATCH"
-    if not args.no_whitted and not args.no_cornell_extra:
+    side = args.full and not args.no_whitted        # the side lines: runs of their own
+    if side and not args.no_cornell_extra:
         out["configs3"] = tiled_line(step, cnt, dev, world, distributed, "configs[3]: Cornell 1920x1080, 256 spp", 256)
-    if not args.no_whitted:
+    if side:
         c4s, c4n, c4cam = rtamd.scenes.complex10k()
         rtamd.scenes.update_camera(c4cam, W, H)
         c4scene = rtamd.SmallptScene(c4s, c4n)
@@ -867,8 +912,8 @@ def main():
         else:
             out["configs4_tiled"] = tiled_line(step, cnt, dev, world, distributed, c4work, SPP, warm=2,
                                                sc=c4scene, cm=c4cam, mode=rtamd.SPT_COUNT_RAYS)
-    if rank == 0 and world == 1:
-        if not args.no_whitted:
+    if rank == 0 and world == 1 and args.full:
+        if side:
             out["whitted"] = whitted_line(args, dev)
             out["configs4"] = c5_line(args, dev)
             out["queue3203"] = queue_line(args, dev)

@@ -19,7 +19,6 @@ import oracle_lib as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 KA = json.load(open(os.path.join(HERE, "golden", "known_answers.json")))["queue3203"]
-REF_BMP = "/root/reference/Raytracer3.2.03/raytracer/OpenCL Raytracer/test.bmp"
 
 
 def _ref():
@@ -31,8 +30,6 @@ def _ref():
 
 def test_reference_build_reproduces_test_bmp(tmp_path):
     Q = _ref()
-    if not os.path.exists(REF_BMP):
-        pytest.skip("reference tree absent")
     P = (O.QPrimitive * 64)()
     n = Q.ref_q_scene(P, 64)
     assert n == 17
@@ -40,9 +37,9 @@ def test_reference_build_reproduces_test_bmp(tmp_path):
     path = str(tmp_path / "test.bmp")
     assert Q.ref_q_write_bmp(px.ctypes.data, 800, 600, path.encode()) == 1
     mine = open(path, "rb").read()
-    ref = open(REF_BMP, "rb").read()
-    assert mine == ref
-    assert hashlib.sha256(ref).hexdigest() == KA["test_bmp"]["sha256"]
+    # the reference's committed test.bmp (1,440,054 bytes) by its recorded size and digest
+    assert len(mine) == KA["test_bmp"]["bytes"]
+    assert hashlib.sha256(mine).hexdigest() == KA["test_bmp"]["sha256"]
 
 
 def test_oracle_frame_matches_known_answers():

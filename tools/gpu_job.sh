@@ -9,7 +9,7 @@
 #   tests               the whole -m gpu suite
 #   tests:FILE[:K]      one test file (optionally -k K)
 #   smoke               __graft_entry__.smoke()
-#   bench               python bench.py (default line)         -> bench.json
+#   bench               python bench.py --full (every line)    -> bench.json
 #   prof                tools/prof_round.sh TAG (bench + rocprofv3 stats + PMC passes)
 #   c4part              tools/c4_partition.py (configs[4] N=4/8 per-rank proxy)
 #   c4time[:GROUP]      tools/c5_time.py, 64 spp, 5 reps (GROUP=k/N: an interleaved share)
@@ -30,7 +30,7 @@ for step in "$@"; do
     tests:*) IFS=: read -r _ f k <<< "$step"
              timeout -k 10 600 $PYT "tests/$f" ${k:+-k "$k"} > "$O/t_$(basename "$f" .py).log" 2>&1 ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$O/smoke.log" 2>&1 ;;
-    bench) timeout -k 10 400 python -u bench.py > "$O/bench.json" 2> "$O/bench.err" ;;
+    bench) timeout -k 10 400 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.err" ;;
     prof) bash tools/prof_round.sh "$TAG" ;;
     c4part) timeout -k 10 400 python -u tools/c4_partition.py > "$O/c4_partition.log" 2>&1 ;;
     c4time*) g=${step#c4time}; g=${g#:}
