@@ -40,11 +40,12 @@
 #include "rt_common.h"
 #include "rt_glibc_math.h"
 #include "rt_levelq.h"
+#include "rt_prims.h"
 
 namespace rt {
 namespace queue {
 
-constexpr int MAXP = 64;        // raytracer.c:720 allocates 50 Primitive_2
+using prims::MAXP;              // raytracer.c:720 allocates 50 Primitive_2
 constexpr int LEVELS = 6;       // depths 0..5 (TRACEDEPTH 5, :4)
 constexpr int NSUB = 9;         // 3 x 3 sub-samples (:317-318)
 constexpr float EPS = 0.001f;   // :26
@@ -52,17 +53,10 @@ constexpr int PLANE = 0, SPHERE = 1;
 constexpr int RING = 32;        // BFS ring per lane in final_kernel (a level-4 node
                                 // leaves at most 32 level-5 slots queued)
 
-struct Scene {
-    // Dense per-type geometry for the nearest-hit loop (ties resolved to the
-    // lowest primitive index, as the reference's strict '<' over ascending s).
-    float4 sph[MAXP];     // centre.xyz, sq_radius
-    float4 pln[MAXP];     // normal.xyz, depth
-    int sph_id[MAXP], pln_id[MAXP];
-    // Non-light primitives (the shadow loop's occluders, :232-240) and their
-    // position in the reference's loop (for the test counter).
-    float4 osph[MAXP], opln[MAXP];
-    int osph_pos[MAXP], opln_pos[MAXP];
-    // Per primitive, for per-lane lookups of the hit primitive.
+// The per-type lists (sphere: centre.xyz, sq_radius; plane: normal.xyz,
+// depth; occluders: the shadow loop's non-light primitives, :232-240) and
+// per-primitive records for per-lane lookups of the hit primitive.
+struct Scene : prims::PrimLists {
     float4 col[MAXP];     // m_color.xyz, m_refl
     float4 mat[MAXP];     // m_refr, m_refr_index, m_diff, m_spec
     float4 geo[MAXP];     // sphere: centre.xyz, r_radius   plane: normal.xyz
@@ -70,8 +64,9 @@ struct Scene {
     int type[MAXP];
     int light[MAXP];
     int lights[MAXP];     // is_light primitives, in index order
-    int n, ns, np, nos, nop, nlights, nnonlight, pad_;
 };
+
+using prims::load_scene;
 
 // One queued ray (Ray, :83-92): what its trace and its term need.
 struct Node {
@@ -115,39 +110,6 @@ __device__ __forceinline__ float spec20(float dp, float pspec, bool &amb)
     return lo;
 }
 
-// Sphere half of intersect (:111-148): the candidate distance (INPRIM: i2,
-// HIT: i1) or +inf with res = 0.
-__device__ __forceinline__ float sphere_cand(float4 g, const ray3 &r, int &res)
-{
-    const float vx = r.o.x - g.x, vy = r.o.y - g.y, vz = r.o.z - g.z;
-    float b = vx * r.d.x + vy * r.d.y + vz * r.d.z;
-    b = -b;
-    const float det = (b * b) - (vx * vx + vy * vy + vz * vz) + g.w;
-    res = 0;
-    float cand = __builtin_inff();
-    if (det > 0) {
-        const float sq = sqrt_exact(det);
-        const float i1 = b - sq, i2 = b + sq;
-        if (i2 > 0) {
-            cand = i1 < 0 ? i2 : i1;
-            res = i1 < 0 ? -1 : 1;
-        }
-    }
-    return cand;
-}
-
-// plane_intersect (:95-109) without branches: the division for every lane,
-// its result kept only where the reference divides (d != 0) and t > 0.  (The
-// per-lane-branch forms of this and of the sphere loops cost more exec-mask
-// instructions than VALU, and an all-occluded exit per occluder sphere or
-// per plane did not pay: profiles/r04.)
-__device__ __forceinline__ float plane_cand_lean(float4 g, const ray3 &r)
-{
-    const float d = g.x * r.d.x + g.y * r.d.y + g.z * r.d.z;
-    const float t = -((g.x * r.o.x + g.y * r.o.y + g.z * r.o.z) + g.w) / d;
-    return (d != 0 && t > 0) ? t : __builtin_inff();
-}
-
 // get_normal, :162-177.
 __device__ __forceinline__ v3 normal_at(const Scene &S, int p, v3 pt)
 {
@@ -158,82 +120,12 @@ __device__ __forceinline__ v3 normal_at(const Scene &S, int p, v3 pt)
     return mk(0.f, 0.f, 0.f);
 }
 
-// raytrace's nearest hit (:181-193: below 1e7, lowest index on ties) for R
-// rays per lane in lock-step: each sphere and plane record read once for all
-// of them, their dependency chains interleaved (R = 2 in the latency-bound
-// root kernel).  sphere_cand as one wave-uniform branch over a straight-line
-// body (sqrt_nr for every lane, its range checked once per loop).  det <= 0
-// or NaN needs no test of its own: sqrt_nr returns NaN there (v_rsq of a
-// negative, 0 x inf at zero), so i2 > 0 fails.
-template <int R>
-__device__ __forceinline__ void nearest_n(const Scene &S, const ray3 (&ray)[R], float (&dist)[R], int (&prim)[R],
-                                          int (&result)[R])
-{
-    bool bad[R];
-#pragma unroll
-    for (int q = 0; q < R; q++) {
-        dist[q] = 10000000.0f;
-        prim[q] = -1;
-        result[q] = 1;
-        bad[q] = false;
-    }
-    for (int k = 0; k < S.ns; k++) {
-        const float4 g = S.sph[k];
-        float b[R], det[R];
-        bool anyp = false;
-#pragma unroll
-        for (int q = 0; q < R; q++) {
-            const float vx = ray[q].o.x - g.x, vy = ray[q].o.y - g.y, vz = ray[q].o.z - g.z;
-            b[q] = vx * ray[q].d.x + vy * ray[q].d.y + vz * ray[q].d.z;
-            b[q] = -b[q];
-            det[q] = (b[q] * b[q]) - (vx * vx + vy * vy + vz * vz) + g.w;
-            anyp = anyp || det[q] > 0;
-        }
-        if (wave_any(anyp)) {
-            const int id = S.sph_id[k];
-#pragma unroll
-            for (int q = 0; q < R; q++) {
-                const float sq = sqrt_nr(det[q]);
-                bad[q] = bad[q] || (det[q] > 0 && !sqrt_nr_ok(det[q]));
-                const float i1 = b[q] - sq, i2 = b[q] + sq;
-                const float c = i1 < 0 ? i2 : i1;
-                const bool take = i2 > 0 && (c < dist[q] || (c == dist[q] && prim[q] >= 0 && id < prim[q]));
-                dist[q] = take ? c : dist[q];
-                prim[q] = take ? id : prim[q];
-                result[q] = take ? (i1 < 0 ? -1 : 1) : result[q];
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < R; q++) {
-        if (wave_any(bad[q])) {                             // (rare: det outside sqrt_nr's range)
-            dist[q] = 10000000.0f;
-            prim[q] = -1;
-            result[q] = 1;
-            for (int k = 0; k < S.ns; k++) {
-                int res;
-                const float c = sphere_cand(S.sph[k], ray[q], res);
-                const int id = S.sph_id[k];
-                if (res && (c < dist[q] || (c == dist[q] && prim[q] >= 0 && id < prim[q]))) {
-                    dist[q] = c; prim[q] = id; result[q] = res;
-                }
-            }
-        }
-    }
-#pragma unroll 4
-    for (int k = 0; k < S.np; k++) {
-        const float4 g = S.pln[k];
-        const int id = S.pln_id[k];
-#pragma unroll
-        for (int q = 0; q < R; q++) {
-            const float c = plane_cand_lean(g, ray[q]);
-            const bool take = c < dist[q] || (c == dist[q] && prim[q] >= 0 && id < prim[q]);
-            dist[q] = take ? c : dist[q];
-            prim[q] = take ? id : prim[q];
-            result[q] = take ? 1 : result[q];
-        }
-    }
-}
+// raytrace's nearest hit (:181-193: below 1e7, lowest index on ties;
+// prims::nearest_n).  prim = -1: no hit.
+struct NearestTraits {
+    static constexpr float far = 10000000.0f;
+    static constexpr int result0 = 1, miss = -1;
+};
 
 // The rest of raytrace (:195-281) from the nearest hit.  EXACT: the specular
 // factor by rtm::pow_d (else spec20's certified shortcut, h.amb when it
@@ -268,56 +160,16 @@ __device__ Hit shade_hit(const Scene &S, const ray3 &ray, float dist, int prim, 
             const float4 lm = S.col[l];
             float shade = 1.0f;
             const v3 t = mk(lc.x - pi.x, lc.y - pi.y, lc.z - pi.z);
-            const float d2 = t.x * t.x + t.y * t.y + t.z * t.z;
-            float len, inv;
-            if (!wave_any(!sqrt_nr_ok(d2))) {                 // :218-223 L_LEN and 1.0f / L_LEN
-                len = sqrt_nr(d2);
-                inv = rcp_nr(len);
-            } else {
-                len = sqrt_rn(d2);
-                inv = 1.0f / len;
-            }
+            float len, inv;                                   // :218-223 L_LEN and 1.0f / L_LEN
+            prims::light_len_inv(t.x * t.x + t.y * t.y + t.z * t.z, len, inv);
             const v3 L = mk(inv * t.x, inv * t.y, inv * t.z);
             if (S.type[l] == SPHERE) {                        // :224-241
                 ray3 r;
                 r.o = mk(pi.x + L.x * EPS, pi.y + L.y * EPS, pi.z + L.z * EPS);
                 r.d = L;
                 shadows++;
-                // Any non-light primitive nearer than the light centre shades
-                // the point; the reference stops at the first, so only its
-                // position matters (test counter).
                 int first = 0x7fffffff;
-                bool sbad = false;
-                for (int k = 0; k < S.nos; k++) {
-                    const float4 g = S.osph[k];
-                    const float vx = r.o.x - g.x, vy = r.o.y - g.y, vz = r.o.z - g.z;
-                    float b = vx * r.d.x + vy * r.d.y + vz * r.d.z;
-                    b = -b;
-                    const float det = (b * b) - (vx * vx + vy * vy + vz * vz) + g.w;
-                    if (wave_any(det > 0)) {
-                        const float sq = sqrt_nr(det);
-                        sbad = sbad || (det > 0 && !sqrt_nr_ok(det));
-                        const float i1 = b - sq, i2 = b + sq;
-                        const float c = i1 < 0 ? i2 : i1;
-                        const bool occ = i2 > 0 && c < len;
-                        first = occ ? min(first, S.osph_pos[k]) : first;
-                    }
-                }
-                if (wave_any(sbad)) {
-                    first = 0x7fffffff;
-                    for (int k = 0; k < S.nos; k++) {
-                        int res;
-                        const float c = sphere_cand(S.osph[k], r, res);
-                        if (res && c < len) first = min(first, S.osph_pos[k]);
-                        if (!COUNT && !wave_any(first == 0x7fffffff)) break;
-                    }
-                }
-                const bool pl_any = COUNT || wave_any(first == 0x7fffffff);   // (all occluded by a sphere: no plane test)
-#pragma unroll 4
-                for (int k = 0; pl_any && k < S.nop; k++) {
-                    const float c = plane_cand_lean(S.opln[k], r);
-                    first = c < len ? min(first, S.opln_pos[k]) : first;
-                }
+                prims::first_occluder<COUNT>(S, r, len, first);
                 if (first != 0x7fffffff) shade = 0.0f;
                 tests += first != 0x7fffffff ? (unsigned)first + 1u : (unsigned)S.nnonlight;
             }
@@ -357,7 +209,7 @@ __device__ Hit trace(const Scene &S, const ray3 &ray)
     const ray3 rr[1] = {ray};
     float dist[1];
     int prim[1], result[1];
-    nearest_n<1>(S, rr, dist, prim, result);
+    prims::nearest_n<1, NearestTraits>(S, rr, dist, prim, result);
     return shade_hit<COUNT, EXACT, UNCERT>(S, ray, dist[0], prim[0], result[0]);
 }
 
@@ -485,21 +337,16 @@ __device__ __forceinline__ Node primary(int sub, int x, int y, float DX, float D
 }
 
 // Scene image from the reference's 96-byte Primitive_2 array: one wave, a
-// lane per primitive (MAXP = 64); each list position is the count of the
-// earlier primitives of its kind (ballot prefix), the reference's order.
-__device__ __forceinline__ void build_scene(const rtq_primitive *__restrict__ prims, int nprims, Scene &S)
+// lane per primitive (prims::fill_lists).
+__device__ __forceinline__ void build_scene(const rtq_primitive *__restrict__ src, int nprims, Scene &S)
 {
-    static_assert(MAXP <= 64, "one lane per primitive");
     const int p = __lane_id();
     const bool v = p < nprims;
     rtq_primitive q{};
-    if (v) q = prims[p];
-    const bool light = v && q.is_light, occluder = v && !q.is_light;
-    const bool sph = v && q.type == SPHERE, pln = v && q.type == PLANE;
-    const unsigned long long below = (1ull << p) - 1ull;       // lanes before this one
-    const auto rank = [&](bool b) { return __popcll(__builtin_amdgcn_ballot_w64(b) & below); };
-    const int il = rank(light), in = rank(occluder), is = rank(sph), ip = rank(pln);
-    const int ios = rank(sph && occluder), iop = rank(pln && occluder);
+    if (v) q = src[p];
+    const int il = prims::fill_lists(S, v, q.type == SPHERE, q.type == PLANE, q.is_light, !q.is_light,
+                                     make_float4(q.center.x, q.center.y, q.center.z, q.sq_radius),
+                                     make_float4(q.normal.x, q.normal.y, q.normal.z, q.depth));
     if (v) {
         S.col[p] = make_float4(q.m_color.x, q.m_color.y, q.m_color.z, q.m_refl);
         S.mat[p] = make_float4(q.m_refr, q.m_refr_index, q.m_diff, q.m_spec);
@@ -507,54 +354,21 @@ __device__ __forceinline__ void build_scene(const rtq_primitive *__restrict__ pr
                                     : make_float4(q.normal.x, q.normal.y, q.normal.z, 0.f);
         S.cen[p] = make_float4(q.center.x, q.center.y, q.center.z, 0.f);
         S.type[p] = q.type;
-        S.light[p] = light ? 1 : 0;
-    }
-    if (light) S.lights[il] = p;
-    if (sph) {
-        const float4 g = make_float4(q.center.x, q.center.y, q.center.z, q.sq_radius);
-        S.sph[is] = g;
-        S.sph_id[is] = p;
-        if (occluder) { S.osph[ios] = g; S.osph_pos[ios] = in; }
-    } else if (pln) {
-        const float4 g = make_float4(q.normal.x, q.normal.y, q.normal.z, q.depth);
-        S.pln[ip] = g;
-        S.pln_id[ip] = p;
-        if (occluder) { S.opln[iop] = g; S.opln_pos[iop] = in; }
-    }
-    const int nl = __popcll(__builtin_amdgcn_ballot_w64(light)), nn = __popcll(__builtin_amdgcn_ballot_w64(occluder));
-    const int ns = __popcll(__builtin_amdgcn_ballot_w64(sph)), np = __popcll(__builtin_amdgcn_ballot_w64(pln));
-    const int nos = __popcll(__builtin_amdgcn_ballot_w64(sph && occluder));
-    const int nop = __popcll(__builtin_amdgcn_ballot_w64(pln && occluder));
-    if (p == 0) {
-        S.n = nprims; S.nlights = nl; S.nnonlight = nn;
-        S.ns = ns; S.np = np; S.nos = nos; S.nop = nop;
+        S.light[p] = q.is_light ? 1 : 0;
+        if (q.is_light) S.lights[il] = p;
     }
 }
 
 // A slab's preparation in one launch: the per-slab counters and flag words
-// zeroed (grid-stride, 16-B stores) and, when `prims` is given, the arena's
-// scene image built by the first wave (it replaces a one-lane scene pass and
-// three fills: ~23 -> ~5 us per 800x600 frame).
-__global__ void __launch_bounds__(256) prep_kernel(const rtq_primitive *__restrict__ prims, int nprims,
+// zeroed and, when `src` is given, the arena's scene image built by the first
+// wave (it replaces a one-lane scene pass and three fills: ~23 -> ~5 us per
+// 800x600 frame).
+__global__ void __launch_bounds__(256) prep_kernel(const rtq_primitive *__restrict__ src, int nprims,
                                                    Scene *__restrict__ scene, uint4 *__restrict__ z0, int n0,
                                                    uint4 *__restrict__ z1, int n1, uint4 *__restrict__ z2, int n2)
 {
-    if (prims && blockIdx.x == 0 && threadIdx.x < 64) build_scene(prims, nprims, *scene);
-    const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n0 + n1 + n2; i += gridDim.x * blockDim.x) {
-        if (i < n0) z0[i] = zero;
-        else if (i < n0 + n1) z1[i - n0] = zero;
-        else z2[i - n0 - n1] = zero;
-    }
-}
-
-__device__ __forceinline__ void load_scene(Scene &S, const Scene *__restrict__ g)
-{
-    static_assert(sizeof(Scene) % 16 == 0, "Scene image is copied in 16-B words");
-    const uint4 *src = (const uint4 *)g;
-    uint4 *dst = (uint4 *)&S;
-    for (int i = threadIdx.x; i < (int)(sizeof(Scene) / 16); i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
+    if (src && blockIdx.x == 0 && threadIdx.x < 64) build_scene(src, nprims, *scene);
+    prims::zero_fill(z0, n0, z1, n1, z2, n2);
 }
 
 // ---------------------------------------------------------------------------
@@ -563,7 +377,6 @@ constexpr int C_FIX = 0;                      // pixels listed for fix_kernel
 constexpr int C_BASE = 1;                     // + L: pool base of level L (2..5; level 1 at 0)
 constexpr int C_SEG = C_BASE + LEVELS;        // + L * NSEG + s: length of segment s of level L (1..5)
 constexpr int C_TOTAL = C_SEG + LEVELS * lq::NSEG;
-#define QCNT(A, i) ((A).count[(i) * lq::CSTRIDE])
 
 // Node record info word: heap index | origin primitive << 8 | type << 16 | rcode << 20.
 __device__ __forceinline__ int pack_info(int node, const Node &n)
@@ -604,7 +417,7 @@ __device__ __forceinline__ int slab_row(const QArgs &A, int r)
 
 __device__ __forceinline__ int level_base(const QArgs &A, int L)
 {
-    return L <= 1 ? 0 : QCNT(A, C_BASE + L);
+    return L <= 1 ? 0 : lq::counter(A, C_BASE + L);
 }
 
 // A tree whose records cannot give the reference's terms -- a node that did
@@ -617,7 +430,7 @@ __device__ void flag_tree(const QArgs &A, int tree)
     const int pix = tree % A.npix;
     const unsigned pb = 1u << (pix & 31);
     if (atomicOr(&A.pixbits[pix >> 5], pb) & pb) return;
-    const int k = atomicAdd(&QCNT(A, C_FIX), 1);
+    const int k = atomicAdd(&lq::counter(A, C_FIX), 1);
     if (k < A.fixcap) A.fixlist[k] = pix;
 }
 
@@ -648,7 +461,7 @@ __device__ __forceinline__ int2 queue_children(const QArgs &A, const Scene &S, i
     const bool ql = active && (f & 1), qr = active && (f & 2);
     const int seg = wave_id & (lq::NSEG - 1);
     const int lim = lq::seg_limit(A.pool, nbase);
-    int j = lq::wave_alloc(&QCNT(A, C_SEG + (L + 1) * lq::NSEG + seg), (int)ql + (int)qr);
+    int j = lq::wave_alloc(&lq::counter(A, C_SEG + (L + 1) * lq::NSEG + seg), (int)ql + (int)qr);
     int2 ch = make_int2(-1, -1);
     if (ql) {
         if (j < lim) {
@@ -711,12 +524,12 @@ root_kernel(QArgs A, int row_end, float DX, float DY, unsigned long long *__rest
         float dd[2];
         int pp[2], rs[2];
         if (s0 + 1 < NSUB) {
-            nearest_n<2>(S, rr, dd, pp, rs);
+            prims::nearest_n<2, NearestTraits>(S, rr, dd, pp, rs);
         } else {
             const ray3 r1[1] = {rr[0]};
             float d1[1];
             int p1[1], q1[1];
-            nearest_n<1>(S, r1, d1, p1, q1);
+            prims::nearest_n<1, NearestTraits>(S, r1, d1, p1, q1);
             dd[0] = d1[0]; pp[0] = p1[0]; rs[0] = q1[0];
         }
 #pragma unroll
@@ -763,9 +576,9 @@ level_kernel(QArgs A, int L)
     __shared__ Scene S;
     load_scene(S, A.scene);
     const int base0 = level_base(A, L);
-    const lq::SegView v = lq::seg_view(&QCNT(A, C_SEG + L * lq::NSEG), base0, lq::seg_limit(A.pool, base0));
+    const lq::SegView v = lq::seg_view(&lq::counter(A, C_SEG + L * lq::NSEG), base0, lq::seg_limit(A.pool, base0));
     const int nbase = lq::next_base(v);             // level L+1's pool base
-    if (L < LEVELS - 1 && blockIdx.x == 0 && threadIdx.x == 0) QCNT(A, C_BASE + L + 1) = nbase;
+    if (L < LEVELS - 1 && blockIdx.x == 0 && threadIdx.x == 0) lq::counter(A, C_BASE + L + 1) = nbase;
     const int lane = __lane_id();
     const int wave_id = (blockIdx.x << 2) + (threadIdx.x >> 6);
     int base, nvalid;
@@ -939,7 +752,7 @@ template <bool COUNT>
 __global__ void __launch_bounds__(64)
 fix_kernel(QArgs A, float DX, float DY, uint32_t *__restrict__ out, unsigned long long *__restrict__ counters)
 {
-    const int nfix = QCNT(A, C_FIX);
+    const int nfix = lq::counter(A, C_FIX);
     if (nfix == 0) return;
     if (blockIdx.x == 0) {
         // A segment counter past its limit: the pool was too small (the next
@@ -947,7 +760,7 @@ fix_kernel(QArgs A, float DX, float DY, uint32_t *__restrict__ out, unsigned lon
         bool over = false;
         for (int L = 1; L < LEVELS; L++) {
             const int base = level_base(A, L);
-            over = over || QCNT(A, C_SEG + L * lq::NSEG + (int)threadIdx.x) > lq::seg_limit(A.pool, base);
+            over = over || lq::counter(A, C_SEG + L * lq::NSEG + (int)threadIdx.x) > lq::seg_limit(A.pool, base);
         }
         if (__builtin_amdgcn_ballot_w64(over) != 0 && threadIdx.x == 0) *(volatile int *)A.ovf = 1;
     }
@@ -1006,7 +819,7 @@ fix_kernel(QArgs A, float DX, float DY, uint32_t *__restrict__ out, unsigned lon
 // ------------------------------------------------------------------ host side
 #include <stdlib.h>
 #include <algorithm>
-#include "rt_runtime.h"
+#include "rt_levelpass.h"
 
 namespace {
 
@@ -1021,57 +834,37 @@ constexpr int SLOT_Q2 = 10;
 constexpr long long SLAB_TREES = 6000000;
 constexpr double POOL_FRAC = 0.8;
 
-int wait_frame(rtrt::DeviceState &st)
-{
-    hipError_t e = hipEventSynchronize(st.wf_done);
-    if (e != hipSuccess) return rtrt::fail_hip(e, "rtq frame wait");
-    st.wf_pending = false;
-    return RT_OK;
-}
-
 int arena(rtrt::DeviceState &st, int slot, int w, int rows, rt::queue::QArgs *A)
 {
     using namespace rt::queue;
     const size_t T = (size_t)w * rows * NSUB;
     if (T > (size_t)0x7fffffff / 2) return rtrt::fail(RT_ERR_INVALID, "rtq: frame too large");
     int *ovf = nullptr;
-    double frac0 = POOL_FRAC;
-    if (const char *e = getenv("RT_QUEUE_POOL_FRAC0")) frac0 = atof(e);                            // A/B
-    size_t P = (size_t)(T * rtrt::pool_fraction(st, rtrt::POOL_QUEUE, (long long)T, frac0, &ovf));
+    size_t P = (size_t)(T * rtrt::pool_fraction(st, rtrt::POOL_QUEUE, (long long)T, POOL_FRAC, &ovf));
     if (const char *e = getenv("RT_QUEUE_POOL_CAP")) {      // test hook: exercises the overflow path
         const long long v = atoll(e);
         if (v > 0 && (size_t)v < P) P = (size_t)v;
     }
     P = std::max<size_t>((P + rt::lq::PAGE_ROW - 1) / rt::lq::PAGE_ROW, 1) * rt::lq::PAGE_ROW;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t npix = (size_t)w * rows;
     const size_t FB = (T + 31) / 32 * 4, PB = (npix + 31) / 32 * 4;
     const size_t FC = std::max<size_t>(npix / 64, 4096);       // listed pixels (fix_kernel)
-    const size_t bytes = al(sizeof(Scene)) + al(T * 16) + al(T * 8) + al(npix * 16) + al(FB) + al(PB) +
-                         al(FC * 4) + al(P * 16) * 3 + al(sizeof(int) * C_TOTAL * rt::lq::CSTRIDE);
-    if (st.cap[slot] < bytes && st.wf_pending) {
-        int rc = wait_frame(st);
-        if (rc) return rc;
-    }
-    void *base = nullptr;
-    int rc = rtrt::scratch(st, slot, bytes, &base);
+    int rc = rtrt::carve_arena(st, slot, [&](rtrt::Arena &a) {
+        a.take(A->scene, sizeof(Scene));
+        a.take(A->rcol, T * 16);
+        a.take(A->rchild, T * 8);
+        a.take(A->psum, npix * 16);
+        a.take(A->fixbits, FB);
+        a.take(A->pixbits, PB);
+        a.take(A->fixlist, FC * 4);
+        a.take(A->ia, P * 16);
+        a.take(A->ib, P * 16);
+        a.take(A->ic, P * 16);
+        a.take(A->count, sizeof(int) * C_TOTAL * rt::lq::CSTRIDE);
+    });
     if (rc) return rc;
-    char *p = (char *)base;
-    auto take = [&](size_t b) { char *q = p; p += al(b); return q; };
-    A->scene = (const Scene *)take(sizeof(Scene));
-    A->rcol = (float4 *)take(T * 16);
-    A->rchild = (int2 *)take(T * 8);
-    A->psum = (float4 *)take((size_t)w * rows * 16);
-    A->fixbits = (unsigned *)take(FB);
-    A->pixbits = (unsigned *)take(PB);
-    A->fixlist = (int *)take(FC * 4);
-    A->ia = (float4 *)take(P * 16);
-    A->ib = (float4 *)take(P * 16);
-    A->ic = (float4 *)take(P * 16);
     A->ncol = A->ia;
     A->nchild = (int2 *)A->ib;
-    A->count = (int *)take(sizeof(int) * C_TOTAL * rt::lq::CSTRIDE);
-    if ((size_t)(p - (char *)base) > bytes) return rtrt::fail(RT_ERR_INVALID, "rtq: arena layout exceeds its size");
     A->ovf = ovf;
     A->pool = (int)P;
     A->fixcap = (int)FC;
@@ -1079,22 +872,12 @@ int arena(rtrt::DeviceState &st, int slot, int w, int rows, rt::queue::QArgs *A)
     return RT_OK;
 }
 
-template <class K>
-int resident_blocks(K kernel)
-{
-    int dev = 0, cus = 0, per = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 1024;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 1024;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, 256, 0) != hipSuccess || per < 1) per = 1;
-    return cus * per;
-}
-
 template <bool COUNT, bool UNCERT>
 int launch(const rt::queue::QArgs &A, int w, int rows, int row_end, float DX, float DY, unsigned long long *cnt,
            hipStream_t s, uint32_t *d_px)
 {
     using namespace rt::queue;
-    static const int level_blocks = resident_blocks(level_kernel<COUNT, UNCERT>);
+    static const int level_blocks = rtrt::resident_blocks(level_kernel<COUNT, UNCERT>);
     const dim3 tiles((w + 15) / 16, (rows + 15) / 16), block(256);
     hipLaunchKernelGGL((root_kernel<COUNT, UNCERT>), tiles, block, 0, s, A, row_end, DX, DY, cnt);
     for (int L = 1; L < LEVELS; L++)
@@ -1118,47 +901,26 @@ extern "C" int rtq_render_async(const rtq_primitive *d_prims, int nprims, uint32
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> lk(st->mu);
     hipStream_t s = (hipStream_t)stream;
-    // The arena belongs to the device: order this frame after the previous
-    // level-pass frame (queue tracer or Whitted), whatever stream it ran on.
-    if (st->wf_pending) {
-        hipError_t e = hipStreamWaitEvent(s, st->wf_done, 0);
-        if (e != hipSuccess) return rtrt::fail_hip(e, "rtq_render_async wait");
-    }
+    rtrt::Frame frame(*st, s, "rtq_render_async");
+    if ((rc = frame.begin())) return rc;
     const float DX = (3.0f - -3.0f) / w, DY = (-2.25f - 2.25f) / h;     // :299-300
     const int rows = row_end - row_begin;
     const int ngroups = (rows + 15) / 16;
-    long long slab_trees = SLAB_TREES;
-    if (const char *e = getenv("RT_QUEUE_SLAB_TREES")) slab_trees = std::max(100000LL, atoll(e));   // A/B
-    long long nslab = ((long long)w * ngroups * 16 * rt::queue::NSUB + slab_trees - 1) / slab_trees;
+    long long nslab = ((long long)w * ngroups * 16 * rt::queue::NSUB + SLAB_TREES - 1) / SLAB_TREES;
     if (const char *e = getenv("RT_QUEUE_SLABS")) nslab = std::max(1, atoi(e));   // test hook
     nslab = std::min<long long>(std::max<long long>(nslab, 1), ngroups);
     // A frame of several slabs alternates them between the caller's stream
     // and a second one, each with its own arena: one slab's latency-bound
     // fold runs beside the other's tracing (1080p, three 6 M-tree slabs:
     // 1.80 -> 1.57 ms at the same 605 MB of arenas; one slab per stream at
-    // 12 M: 1.50 ms but 1.2 GB). RT_QUEUE_STREAMS=1/2 overrides (A/B; 2
-    // forces at least two slabs).
-    int nstream = nslab >= 2 ? 2 : 1;
-    if (const char *e = getenv("RT_QUEUE_STREAMS")) nstream = atoi(e) >= 2 ? 2 : 1;
-    if (nstream == 2) {
-        nslab = std::min<long long>(std::max<long long>(nslab, 2), ngroups);
-        if (nslab < 2) nstream = 1;
-    }
-    const int slab_rows = (int)((ngroups + nslab - 1) / nslab) * 16;
+    // 12 M: 1.50 ms but 1.2 GB).
+    const int nstream = nslab >= 2 ? 2 : 1;
+    const int slab_rows = rtrt::slab_rows(ngroups, 0, nslab);
     rt::queue::QArgs A[2];
-    hipStream_t ss[2] = {s, s};
-    if (nstream == 2) {
-        if ((rc = rtrt::aux_stream(*st))) return rc;
-        ss[1] = st->aux;
-        hipError_t e = hipEventRecord(st->fork_ev, s);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st->aux, st->fork_ev, 0);
-        if (e != hipSuccess) return rtrt::fail_hip(e, "rtq_render_async fork");
-    }
+    if (nstream == 2 && (rc = frame.fork())) return rc;
     unsigned long long *cnt = (unsigned long long *)d_counters;
-    // (after the fork, an error return still joins the second stream back)
-    const auto bail = [&](int code) { return nstream == 2 ? rtrt::join_aux_on_error(*st, s, code) : code; };
     for (int i = 0; i < nstream; i++) {
-        if ((rc = arena(*st, i ? SLOT_Q2 : SLOT_Q, w, slab_rows, &A[i]))) return bail(rc);
+        if ((rc = arena(*st, i ? SLOT_Q2 : SLOT_Q, w, slab_rows, &A[i]))) return frame.bail(rc);
         A[i].row_stride = (int)nslab;
     }
     // RT_QUEUE_EXACT_ALL=1 (test hook): every specular term uncertified,
@@ -1166,17 +928,16 @@ extern "C" int rtq_render_async(const rtq_primitive *d_prims, int nprims, uint32
     const char *ex = getenv("RT_QUEUE_EXACT_ALL");
     for (int k = 0; k < (int)nslab; k++) {
         rt::queue::QArgs &a = A[k % nstream];
-        hipStream_t sk = ss[k % nstream];
-        const int srows = (int)((ngroups - k + nslab - 1) / nslab) * 16;
+        hipStream_t sk = frame.ss[k % nstream];
+        const int srows = rtrt::slab_rows(ngroups, k, nslab);
         a.row_begin = row_begin + 16 * k;
         a.npix = w * srows;
         a.ntrees = a.npix * rt::queue::NSUB;
         // counters, tree and pixel flag words zeroed; the arena's scene image
         // built by its first slab (16-B words: the arena rounds every part to 256 B)
-        const auto words = [](size_t bytes) { return (int)((bytes + 15) / 16); };
-        const int nz0 = words(sizeof(int) * rt::queue::C_TOTAL * rt::lq::CSTRIDE);
-        const int nz1 = words(sizeof(unsigned) * (((size_t)a.ntrees + 31) / 32));
-        const int nz2 = words(sizeof(unsigned) * (((size_t)a.npix + 31) / 32));
+        const int nz0 = rtrt::words16(sizeof(int) * rt::queue::C_TOTAL * rt::lq::CSTRIDE);
+        const int nz1 = rtrt::words16(sizeof(unsigned) * (((size_t)a.ntrees + 31) / 32));
+        const int nz2 = rtrt::words16(sizeof(unsigned) * (((size_t)a.npix + 31) / 32));
         const int pblocks = std::min(1024, std::max(1, (nz0 + nz1 + nz2 + 255) / 256));
         hipLaunchKernelGGL(rt::queue::prep_kernel, dim3(pblocks), dim3(256), 0, sk, k < nstream ? d_prims : nullptr,
                            nprims, (rt::queue::Scene *)a.scene, (uint4 *)a.count, nz0, (uint4 *)a.fixbits, nz1,
@@ -1187,17 +948,9 @@ extern "C" int rtq_render_async(const rtq_primitive *d_prims, int nprims, uint32
         else
             rc = cnt ? launch<true, false>(a, w, srows, row_end, DX, DY, cnt, sk, d_pixels)
                      : launch<false, false>(a, w, srows, row_end, DX, DY, cnt, sk, d_pixels);
-        if (rc) return bail(rc);
+        if (rc) return frame.bail(rc);
     }
-    if (nstream == 2) {
-        hipError_t e = hipEventRecord(st->join_ev, st->aux);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s, st->join_ev, 0);
-        if (e != hipSuccess) return bail(rtrt::fail_hip(e, "rtq_render_async join"));
-    }
-    hipError_t e = hipEventRecord(st->wf_done, s);
-    if (e != hipSuccess) return rtrt::fail_hip(e, "rtq_render_async record");
-    st->wf_pending = true;
-    return RT_OK;
+    return frame.end();
 }
 
 extern "C" int rtq_render(const rtq_primitive *prims, int nprims, uint32_t *pixels, int w, int h,
@@ -1205,28 +958,8 @@ extern "C" int rtq_render(const rtq_primitive *prims, int nprims, uint32_t *pixe
 {
     if (!prims || !pixels || nprims < 1 || nprims > rt::queue::MAXP || w < 1 || h < 1)
         return rtrt::fail(RT_ERR_INVALID, "rtq_render: bad arguments");
-    rtrt::DeviceState *st;
-    int rc = rtrt::state(&st);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lk(st->mu);
-    // slots 0..2 may still feed a frame issued on another stream
-    if (st->wf_pending && (rc = wait_frame(*st))) return rc;
-    const size_t frame_bytes = sizeof(uint32_t) * (size_t)w * h;
-    void *d_prims, *d_px, *d_cnt;
-    if ((rc = rtrt::scratch(*st, 0, sizeof(rtq_primitive) * nprims, &d_prims))) return rc;
-    if ((rc = rtrt::scratch(*st, 1, frame_bytes, &d_px))) return rc;
-    if ((rc = rtrt::scratch(*st, 2, 4 * sizeof(uint64_t), &d_cnt))) return rc;
-    hipStream_t s = st->stream;
-    hipError_t e = hipMemcpyAsync(d_prims, prims, sizeof(rtq_primitive) * nprims, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && counters) e = hipMemsetAsync(d_cnt, 0, 4 * sizeof(uint64_t), s);
-    if (e != hipSuccess) return rtrt::fail_hip(e, "rtq_render H2D");
-    rc = rtq_render_async((const rtq_primitive *)d_prims, nprims, (uint32_t *)d_px, w, h, 0, h,
-                          counters ? (uint64_t *)d_cnt : nullptr, s);
-    if (rc) return rc;
-    e = hipMemcpyAsync(pixels, d_px, frame_bytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && counters)
-        e = hipMemcpyAsync(counters, d_cnt, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return rtrt::fail_hip(e, "rtq_render D2H");
-    return RT_OK;
+    return rtrt::render_blocking("rtq_render", prims, nprims, pixels, w, h, 0, h, counters,
+                                 [&](const rtq_primitive *d_prims, uint32_t *d_px, uint64_t *d_cnt, hipStream_t s) {
+                                     return rtq_render_async(d_prims, nprims, d_px, w, h, 0, h, d_cnt, s);
+                                 });
 }

@@ -25,6 +25,14 @@ constexpr int PAGE_ROW = NSEG * PAGE; // one page of every segment
 constexpr int CSTRIDE = 32;           // ints between counters: one 128-B line each
                                       // (same-line atomics serialise in the L2)
 
+// Counter i of a pass's count[] (its args struct A holds `int *count`; the
+// layout of the indices is the tracer's own).
+template <class Args>
+__device__ __forceinline__ int &counter(const Args &A, int i)
+{
+    return A.count[i * CSTRIDE];
+}
+
 // Pool slot of item j of segment s of the level based at `base`.
 __device__ __forceinline__ int seg_slot(int base, int s, int j)
 {

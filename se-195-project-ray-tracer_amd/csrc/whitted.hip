@@ -29,28 +29,20 @@
 #include "rt_common.h"
 #include "rt_glibc_math.h"
 #include "rt_levelq.h"
+#include "rt_prims.h"
 
 namespace rt {
 namespace whitted {
 
-constexpr int MAXP = 64;        // reference allocates 50 (scene.cpp:225)
+using prims::MAXP;              // reference allocates 50 (scene.cpp:225)
 constexpr int NODES = 63;       // raytracer.cpp:336
 constexpr float EPS = 0.001f;   // common.h:24
 constexpr int SPHERE = 1, PLANE = 2;
 
-struct Scene {
-    // Geometry in dense per-type arrays (no index indirection in the hot
-    // loops): the nearest-hit and occlusion results are independent of the
-    // visiting order once distance ties go to the lowest primitive index
-    // (the reference's strict '<' over ascending s, raytracer.cpp:39-49).
-    float4 sph[MAXP];   // sphere centre.xyz, SqRadius
-    float4 pln[MAXP];   // plane N.xyz, D
-    int sph_id[MAXP], pln_id[MAXP];        // original primitive index
-    float4 osph[MAXP];  // non-light spheres (occluders, raytracer.cpp:100)
-    float4 opln[MAXP];  // non-light planes
-    int osph_pos[MAXP], opln_pos[MAXP];    // position in the non-light order (test counts)
-    int ns, np, nos, nop;
-    // Per-primitive records for per-lane lookups of the hit primitive.
+// The per-type lists (sphere: centre.xyz, SqRadius; plane: N.xyz, D;
+// occluders: raytracer.cpp:100) and per-primitive records for per-lane
+// lookups of the hit primitive.
+struct Scene : prims::PrimLists {
     float4 geo[MAXP];   // sphere: centre.xyz, SqRadius   plane: N.xyz, D
     float4 mat0[MAXP];  // colour.xyz, refl
     float4 mat1[MAXP];  // refr, diff, spec, rindex
@@ -59,40 +51,9 @@ struct Scene {
     int type[MAXP];
     int light[MAXP];
     int lights[MAXP];   // indices of m_Light > 0 primitives, in index order
-    int n, nnonlight, nlights;
-    int pad_;                                     // sizeof(Scene) % 16 == 0
 };
 
-// Sphere half of Primitive_Intersect (scene.cpp:130-169): the candidate
-// distance (INPRIM: i2, HIT: i1) or +inf with res = 0.
-__device__ __forceinline__ float sphere_cand(float4 g, const ray3 &r, int &res)
-{
-    const float vx = r.o.x - g.x, vy = r.o.y - g.y, vz = r.o.z - g.z;
-    float b = vx * r.d.x + vy * r.d.y + vz * r.d.z;
-    b = -b;
-    float det = (b * b) - (vx * vx + vy * vy + vz * vz) + g.w;
-    res = 0;
-    float cand = __builtin_inff();
-    if (det > 0) {
-        det = sqrt_exact(det);
-        const float i1 = b - det, i2 = b + det;
-        if (i2 > 0) {
-            cand = i1 < 0 ? i2 : i1;
-            res = i1 < 0 ? -1 : 1;
-        }
-    }
-    return cand;
-}
-
-// Plane half of Primitive_Intersect (scene.cpp:171-185), without branches:
-// the division for every lane, its result kept only where the reference
-// divides (d != 0) and t > 0.
-__device__ __forceinline__ float plane_cand_lean(float4 g, const ray3 &r)
-{
-    const float d = g.x * r.d.x + g.y * r.d.y + g.z * r.d.z;
-    const float t = -((g.x * r.o.x + g.y * r.o.y + g.z * r.o.z) + g.w) / d;
-    return (d != 0 && t > 0) ? t : __builtin_inff();
-}
+using prims::load_scene;
 
 // Primitive_GetNormal, scene.cpp:34-53.
 __device__ __forceinline__ v3 normal_at(const Scene &S, int p, v3 pos)
@@ -122,84 +83,11 @@ struct Hit {
 struct Counts { unsigned long long traced, shadow, tests, tir; };
 
 // Engine_Raytrace's nearest hit (raytracer.cpp:39-49: min distance below 1e6,
-// lowest index on ties) for R rays per lane in lock-step: each sphere and
-// plane record is read once for all of them and their dependency chains
-// interleave (R = 2 in the latency-bound root kernel).  Branch-lean: a
-// sphere is one wave-uniform branch (skipped when no lane's det is
-// positive) around a straight-line body -- sqrt_nr for every lane, its range
-// checked once per loop, a lane outside it redoing its ray with the exact
-// per-sphere test -- and a plane test is straight-line (the division for
-// every lane, kept where the reference divides).  det <= 0 or NaN needs no
-// test of its own: sqrt_nr returns NaN there, so i2 > 0 fails.  (The
-// per-lane-branch forms cost more exec-mask instructions than VALU:
-// profiles/r04/whitted_lean_loops_ab.log.)  prim = 0x7fffffff: no hit.
-template <int R>
-__device__ __forceinline__ void nearest_n(const Scene &S, const ray3 (&ray)[R], float (&dist)[R], int (&prim)[R],
-                                          int (&result)[R])
-{
-    bool bad[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        dist[r] = 1000000.0f;
-        prim[r] = 0x7fffffff;
-        result[r] = 0;
-        bad[r] = false;
-    }
-    for (int k = 0; k < S.ns; k++) {
-        const float4 g = S.sph[k];
-        float b[R], det[R];
-        bool anyp = false;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const float vx = ray[r].o.x - g.x, vy = ray[r].o.y - g.y, vz = ray[r].o.z - g.z;
-            b[r] = vx * ray[r].d.x + vy * ray[r].d.y + vz * ray[r].d.z;
-            b[r] = -b[r];
-            det[r] = (b[r] * b[r]) - (vx * vx + vy * vy + vz * vz) + g.w;
-            anyp = anyp || det[r] > 0;
-        }
-        if (wave_any(anyp)) {
-            const int id = S.sph_id[k];
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const float sd = sqrt_nr(det[r]);
-                bad[r] = bad[r] || (det[r] > 0 && !sqrt_nr_ok(det[r]));
-                const float i1 = b[r] - sd, i2 = b[r] + sd;
-                const float c = i1 < 0 ? i2 : i1;
-                const bool take = i2 > 0 && (c < dist[r] || (c == dist[r] && id < prim[r]));
-                dist[r] = take ? c : dist[r];
-                prim[r] = take ? id : prim[r];
-                result[r] = take ? (i1 < 0 ? -1 : 1) : result[r];
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        if (wave_any(bad[r])) {                         // (rare: det outside sqrt_nr's range)
-            dist[r] = 1000000.0f;
-            prim[r] = 0x7fffffff;
-            result[r] = 0;
-            for (int k = 0; k < S.ns; k++) {
-                int res;
-                const float c = sphere_cand(S.sph[k], ray[r], res);
-                const int id = S.sph_id[k];
-                if (res && (c < dist[r] || (c == dist[r] && id < prim[r]))) { dist[r] = c; prim[r] = id; result[r] = res; }
-            }
-        }
-    }
-#pragma unroll 4
-    for (int k = 0; k < S.np; k++) {
-        const float4 g = S.pln[k];
-        const int id = S.pln_id[k];
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const float c = plane_cand_lean(g, ray[r]);
-            const bool take = c < dist[r] || (c == dist[r] && id < prim[r]);
-            dist[r] = take ? c : dist[r];
-            prim[r] = take ? id : prim[r];
-            result[r] = take ? 1 : result[r];
-        }
-    }
-}
+// lowest index on ties; prims::nearest_n).  prim = 0x7fffffff: no hit.
+struct NearestTraits {
+    static constexpr float far = 1000000.0f;
+    static constexpr int result0 = 0, miss = 0x7fffffff;
+};
 
 // The rest of Engine_Raytrace (raytracer.cpp:51-271) from its nearest hit
 // (a_Depth is always 1 at every call site, so the TRACEDEPTH guards are
@@ -253,61 +141,15 @@ __device__ Hit shade_hit(const Scene &S, const ray3 &ray, float rindex_in, float
         // in the shadow test (:76-82) and the shading (:115-125), done once.
         v3 L = mk(lg.x - pi.x, lg.y - pi.y, lg.z - pi.z);
         float len, inv;
-        {
-            const float d2 = L.x * L.x + L.y * L.y + L.z * L.z;
-            if (!wave_any(!sqrt_nr_ok(d2))) {
-                len = sqrt_nr(d2);
-                inv = rcp_nr(len);
-            } else {
-                len = sqrt_rn(d2);
-                inv = 1.0f / len;
-            }
-        }
+        prims::light_len_inv(L.x * L.x + L.y * L.y + L.z * L.z, len, inv);
         L.x *= inv; L.y *= inv; L.z *= inv;
         if (S.type[l] == SPHERE) {                      // :76-110
-            const float tdist = len;
             ray3 r;
             r.o = mk(pi.x + L.x * EPS, pi.y + L.y * EPS, pi.z + L.z * EPS);
             r.d = L;
             cnt.shadow++;
-            // Any non-light primitive nearer than the light centre shades the
-            // point (the reference breaks at the first one; which one does not
-            // matter, only the count of tests, recovered from its position).
-            // The loops are nearest_n's lean forms.  (An all-occluded exit
-            // after each sphere measured slower; the planes take one
-            // all-occluded check before their loop.)
             int first = 0x7fffffff;
-            bool sbad = false;
-            for (int k = 0; k < S.nos; k++) {
-                const float4 g = S.osph[k];
-                const float vx = r.o.x - g.x, vy = r.o.y - g.y, vz = r.o.z - g.z;
-                float b = vx * r.d.x + vy * r.d.y + vz * r.d.z;
-                b = -b;
-                const float det = (b * b) - (vx * vx + vy * vy + vz * vz) + g.w;
-                if (wave_any(det > 0)) {
-                    const float sd = sqrt_nr(det);
-                    sbad = sbad || (det > 0 && !sqrt_nr_ok(det));
-                    const float i1 = b - sd, i2 = b + sd;
-                    const float c = i1 < 0 ? i2 : i1;
-                    const bool occ = i2 > 0 && c < tdist;
-                    first = occ ? min(first, S.osph_pos[k]) : first;
-                }
-            }
-            if (wave_any(sbad)) {
-                first = 0x7fffffff;
-                for (int k = 0; k < S.nos; k++) {
-                    int res;
-                    const float c = sphere_cand(S.osph[k], r, res);
-                    if (res && c < tdist) first = min(first, S.osph_pos[k]);
-                    if (!COUNT && !wave_any(first == 0x7fffffff)) break;
-                }
-            }
-            const bool pl_any = COUNT || wave_any(first == 0x7fffffff);   // (all occluded by a sphere: no plane test)
-#pragma unroll 4
-            for (int k = 0; pl_any && k < S.nop; k++) {
-                const float c = plane_cand_lean(S.opln[k], r);
-                first = c < tdist ? min(first, S.opln_pos[k]) : first;
-            }
+            prims::first_occluder<COUNT>(S, r, len, first);
             if (first != 0x7fffffff) shade = 0;
             cnt.tests += (unsigned long long)(first != 0x7fffffff ? first + 1 : S.nnonlight);
         }
@@ -371,7 +213,7 @@ __device__ Hit trace(const Scene &S, const ray3 &ray, float rindex_in, Counts &c
     const ray3 rr[1] = {ray};
     float dist[1];
     int prim[1], result[1];
-    nearest_n<1>(S, rr, dist, prim, result);
+    prims::nearest_n<1, NearestTraits>(S, rr, dist, prim, result);
     return shade_hit<COUNT>(S, ray, rindex_in, dist[0], prim[0], result[0], cnt, ocl);
 }
 
@@ -393,23 +235,16 @@ __device__ __forceinline__ ray3 primary(int sub, float SX, float SY, float DX, f
 }
 
 // Builds the SoA scene image from the reference's 96-byte AoS primitives:
-// one wave, a lane per primitive (MAXP = 64); each list position is the
-// count of the earlier primitives of its kind (ballot prefix), so the lists
-// keep the reference's order.
-__device__ void build_scene(Scene &S, const rt_primitive *__restrict__ prims, int nprims)
+// one wave, a lane per primitive (prims::fill_lists).
+__device__ void build_scene(Scene &S, const rt_primitive *__restrict__ src, int nprims)
 {
-    static_assert(MAXP <= 64, "one lane per primitive");
     const int p = __lane_id();
     const bool v = p < nprims;
     rt_primitive q{};
-    if (v) q = prims[p];
-    const bool light = v && q.m_Light > 0, occluder = v && q.m_Light == 0;
-    const bool sph = v && q.type == SPHERE, pln = v && q.type == PLANE;
-    const unsigned long long below = (1ull << p) - 1ull;       // lanes before this one
-    const auto rank = [&](bool b) { return __popcll(__builtin_amdgcn_ballot_w64(b) & below); };
-    const auto total = [](bool b) { return __popcll(__builtin_amdgcn_ballot_w64(b)); };
-    const int il = rank(light), in = rank(occluder), is = rank(sph), ip = rank(pln);
-    const int ios = rank(sph && occluder), iop = rank(pln && occluder);
+    if (v) q = src[p];
+    const int il = prims::fill_lists(S, v, q.type == SPHERE, q.type == PLANE, q.m_Light > 0, q.m_Light == 0,
+                                     make_float4(q.m_Centre.x, q.m_Centre.y, q.m_Centre.z, q.m_SqRadius),
+                                     make_float4(q.plane_N.x, q.plane_N.y, q.plane_N.z, q.plane_D));
     if (v) {
         S.geo[p] = q.type == SPHERE ? make_float4(q.m_Centre.x, q.m_Centre.y, q.m_Centre.z, q.m_SqRadius)
                                     : make_float4(q.plane_N.x, q.plane_N.y, q.plane_N.z, q.plane_D);
@@ -419,51 +254,19 @@ __device__ void build_scene(Scene &S, const rt_primitive *__restrict__ prims, in
         S.rrad[p] = q.m_RRadius;
         S.type[p] = q.type;
         S.light[p] = q.m_Light;
-    }
-    if (light) S.lights[il] = p;
-    if (sph) {
-        const float4 g = make_float4(q.m_Centre.x, q.m_Centre.y, q.m_Centre.z, q.m_SqRadius);
-        S.sph[is] = g;
-        S.sph_id[is] = p;
-        if (occluder) { S.osph[ios] = g; S.osph_pos[ios] = in; }
-    } else if (pln) {
-        const float4 g = make_float4(q.plane_N.x, q.plane_N.y, q.plane_N.z, q.plane_D);
-        S.pln[ip] = g;
-        S.pln_id[ip] = p;
-        if (occluder) { S.opln[iop] = g; S.opln_pos[iop] = in; }
-    }
-    const int nl = total(light), nn = total(occluder), ns = total(sph), np = total(pln);
-    const int nos = total(sph && occluder), nop = total(pln && occluder);
-    if (p == 0) {
-        S.n = nprims; S.nlights = nl; S.nnonlight = nn;
-        S.ns = ns; S.np = np; S.nos = nos; S.nop = nop;
+        if (q.m_Light > 0) S.lights[il] = p;
     }
 }
 
 // A slab's preparation in one launch: its counters and tree flag words
-// zeroed (grid-stride, 16-B stores) and, when `prims` is given, the arena's
-// scene image built by the first wave (replaces a one-lane scene pass and
-// two fills).
-__global__ void __launch_bounds__(256) prep_kernel(const rt_primitive *__restrict__ prims, int nprims,
+// zeroed and, when `src` is given, the arena's scene image built by the
+// first wave (replaces a one-lane scene pass and two fills).
+__global__ void __launch_bounds__(256) prep_kernel(const rt_primitive *__restrict__ src, int nprims,
                                                    Scene *__restrict__ scene, uint4 *__restrict__ z0, int n0,
                                                    uint4 *__restrict__ z1, int n1)
 {
-    if (prims && blockIdx.x == 0 && threadIdx.x < 64) build_scene(*scene, prims, nprims);
-    const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n0 + n1; i += gridDim.x * blockDim.x) {
-        if (i < n0) z0[i] = zero;
-        else z1[i - n0] = zero;
-    }
-}
-
-// Block-cooperative copy of the scene image into LDS (coalesced 16-B loads).
-__device__ __forceinline__ void load_scene(Scene &S, const Scene *__restrict__ g)
-{
-    static_assert(sizeof(Scene) % 16 == 0, "Scene image is copied in 16-B words");
-    const uint4 *src = (const uint4 *)g;
-    uint4 *dst = (uint4 *)&S;
-    for (int i = threadIdx.x; i < (int)(sizeof(Scene) / 16); i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
+    if (src && blockIdx.x == 0 && threadIdx.x < 64) build_scene(*scene, src, nprims);
+    prims::zero_fill(z0, n0, z1, n1);
 }
 
 // ---------------------------------------------------------------------------
@@ -516,13 +319,13 @@ using lq::seg_slot;
 using lq::wave_alloc;
 using lq::next_base;
 using lq::seg_chunk;
+using lq::counter;
 // count[] layout (zeroed per slab), one counter per 128-B line (lq::CSTRIDE).
 constexpr int C_FIX = 0;                      // trees flagged for fixup
 constexpr int C_TIR = 1;                      // + L: TIR list length of level L (0..4)
 constexpr int C_BASE = C_TIR + LEVELS;        // + L: pool base of level L (2..5; level 1 at 0)
 constexpr int C_SEG = C_BASE + LEVELS;        // + L * NSEG + s: length of segment s of level L (1..5)
 constexpr int C_TOTAL = C_SEG + LEVELS * NSEG;
-#define CNT(A, i) ((A).count[(i) * CSTRIDE])
 
 struct WfArgs {
     const Scene *scene;       // scene image (prep_kernel, the arena's first slab)
@@ -569,14 +372,14 @@ __device__ __forceinline__ int seg_limit(const WfArgs &A, int base)
 }
 __device__ __forceinline__ int level_base(const WfArgs &A, int L)
 {
-    return L <= 1 ? 0 : CNT(A, C_BASE + L);
+    return L <= 1 ? 0 : counter(A, C_BASE + L);
 }
 
 __device__ void flag_tree(const WfArgs &A, int tree)
 {
     const unsigned bit = 1u << (tree & 31);
     if (!(atomicOr(&A.fixbits[tree >> 5], bit) & bit)) {
-        const int s = atomicAdd(&CNT(A, C_FIX), 1);
+        const int s = atomicAdd(&counter(A, C_FIX), 1);
         if (s < A.fixcap) A.fixlist[s] = tree;
     }
 }
@@ -607,7 +410,7 @@ __device__ __forceinline__ int2 queue_children(const WfArgs &A, int L, int nbase
     const bool qr = cr && !tir;
     const int seg = wave_id & (NSEG - 1);
     const int lim = seg_limit(A, nbase);
-    int j = wave_alloc(&CNT(A, C_SEG + (L + 1) * NSEG + seg), (int)cl + (int)qr);
+    int j = wave_alloc(&counter(A, C_SEG + (L + 1) * NSEG + seg), (int)cl + (int)qr);
     int2 ch = make_int2(-1, -1);
     if (cl) {
         if (j < lim) {
@@ -627,7 +430,7 @@ __device__ __forceinline__ int2 queue_children(const WfArgs &A, int L, int nbase
         }
     }
     if (cr && tir) {
-        const int t = atomicAdd(&CNT(A, C_TIR + L), 1);
+        const int t = atomicAdd(&counter(A, C_TIR + L), 1);
         if (t < A.tcap) A.tir[L][t] = make_int4(slot_self, tree, node, __float_as_int(hh.rindex_out));
         else flag_tree(A, tree);
     }
@@ -643,7 +446,7 @@ __device__ __forceinline__ int node_info(const Hit &hh, bool tir)
 __device__ __forceinline__ SegView seg_view(const WfArgs &A, int L)
 {
     const int base = level_base(A, L);
-    return lq::seg_view(&CNT(A, C_SEG + L * NSEG), base, seg_limit(A, base));
+    return lq::seg_view(&counter(A, C_SEG + L * NSEG), base, seg_limit(A, base));
 }
 
 #ifndef RT_WH_MINWAVES
@@ -688,7 +491,7 @@ root_kernel(WfArgs A, int row_end, const float *__restrict__ sx_tab, const float
         int np_[RT_WH_ROOT_RAYS], nr[RT_WH_ROOT_RAYS];
 #pragma unroll
         for (int j = 0; j < RT_WH_ROOT_RAYS; j++) rp[j] = primary(min(sub0 + j, A.nsub - 1), SX, SY, DX, DY, A.side);
-        nearest_n<RT_WH_ROOT_RAYS>(S, rp, nd, np_, nr);
+        prims::nearest_n<RT_WH_ROOT_RAYS, NearestTraits>(S, rp, nd, np_, nr);
 #pragma unroll
         for (int j = 0; j < RT_WH_ROOT_RAYS; j++) {
             const int sub = sub0 + j;
@@ -734,7 +537,7 @@ level_kernel(WfArgs A, int L, unsigned long long *__restrict__ counters)
     load_scene(S, A.scene);
     const SegView v = seg_view(A, L);
     const int nbase = next_base(v);                 // level L+1's pool base
-    if (L < LEVELS - 1 && blockIdx.x == 0 && threadIdx.x == 0) CNT(A, C_BASE + L + 1) = nbase;
+    if (L < LEVELS - 1 && blockIdx.x == 0 && threadIdx.x == 0) counter(A, C_BASE + L + 1) = nbase;
     const int lane = __lane_id();
     const int wave_id = (blockIdx.x << 2) + (threadIdx.x >> 6);
     Counts cnt = {0, 0, 0, 0};
@@ -796,7 +599,7 @@ __global__ void __launch_bounds__(64)
 tir_kernel(WfArgs A, int L, const float *__restrict__ sx_tab, const float *__restrict__ sy_tab, float DX,
            float DY)
 {
-    const int nt = min(CNT(A, C_TIR + L), A.tcap);
+    const int nt = min(counter(A, C_TIR + L), A.tcap);
     const int nbase = level_base(A, L + 1);
     const int lim = seg_limit(A, nbase);
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < nt; t += gridDim.x * blockDim.x) {
@@ -824,7 +627,7 @@ tir_kernel(WfArgs A, int L, const float *__restrict__ sx_tab, const float *__res
             r = primary(sub, sx_tab[x], sy_tab[y], DX, DY, A.side);
         }
         const int seg = tree & (NSEG - 1);
-        const int k = atomicAdd(&CNT(A, C_SEG + (L + 1) * NSEG + seg), 1);
+        const int k = atomicAdd(&counter(A, C_SEG + (L + 1) * NSEG + seg), 1);
         if (k >= lim) { flag_tree(A, tree); continue; }
         const int q = seg_slot(nbase, seg, k);
         put_item(A, L + 1, q, r, rin, tree, 2 * node + 2);
@@ -890,10 +693,9 @@ __device__ __forceinline__ float4 folded(const WfArgs &A, const Scene &S, int c)
 }
 
 // Back-accumulation of level L's nodes with their D levels below
-// (folded<D>), written back: D = 1 is a launch per level (4, 3, 2, 1); D = 2
-// folds levels (3 <- 4 <- 5) and (1 <- 2 <- 3) in two launches, the default
-// (WF_BACKACC_LEVELS).  Levels written: only those a later launch or
-// final_kernel reads as final.
+// (folded<D>), written back: D = 2, the one launched, folds levels
+// (3 <- 4 <- 5) and (1 <- 2 <- 3) in two launches.  Levels written: only
+// those a later launch or final_kernel reads as final.
 template <int D>
 __global__ void __launch_bounds__(256)
 backacc_kernel(WfArgs A, int L)
@@ -996,17 +798,17 @@ __global__ void __launch_bounds__(64)
 fixup_kernel(WfArgs A, const float *__restrict__ sx_tab, const float *__restrict__ sy_tab, float DX, float DY,
              unsigned long long *__restrict__ counters)
 {
-    const int nfix = CNT(A, C_FIX);
+    const int nfix = counter(A, C_FIX);
     if (nfix == 0) return;
     if (blockIdx.x == 0) {
         // Tell the host when a queue asked for more than its pages (a segment
         // counter past its limit) or a TIR list for more than its capacity:
         // the next frame gets a larger pool.
         const int lane = threadIdx.x;
-        bool over = lane < LEVELS - 1 && CNT(A, C_TIR + lane) > A.tcap;
+        bool over = lane < LEVELS - 1 && counter(A, C_TIR + lane) > A.tcap;
         for (int L = 1; L < LEVELS; L++) {
             const int base = level_base(A, L);
-            over = over || CNT(A, C_SEG + L * NSEG + lane) > seg_limit(A, base);
+            over = over || counter(A, C_SEG + L * NSEG + lane) > seg_limit(A, base);
         }
         if (__builtin_amdgcn_ballot_w64(over) != 0 && lane == 0) *(volatile int *)A.ovf = 1;
     }
@@ -1119,7 +921,7 @@ fixup_kernel(WfArgs A, const float *__restrict__ sx_tab, const float *__restrict
 // ------------------------------------------------------------------ host side
 #include <stdlib.h>
 #include <algorithm>
-#include "rt_runtime.h"
+#include "rt_levelpass.h"
 
 namespace {
 
@@ -1133,13 +935,6 @@ constexpr int SLOT_WF2 = 9;
 // frame's mix of sphere / plane / background rows and so its queue fill.
 constexpr long long SLAB_TREES = 18000000;
 constexpr long long STREAM2_TREES = 4000000;   // frames from this size on: two slabs on two streams
-#ifndef WF_SPLIT_P
-#define WF_SPLIT_P 1                            // row groups of the first / second of those slabs per period
-#define WF_SPLIT_Q 1
-#endif
-#ifndef WF_BACKACC_LEVELS
-#define WF_BACKACC_LEVELS 2                     // levels folded per back-accumulation launch (1 or 2)
-#endif
 // Record pool (levels 1..5 together) as a fraction of the slab's trees, to
 // start with.  The reference scene needs 0.83 at 1080p (14.2 M nodes for
 // 17.1 M trees) but 0.94 at 640 x 480 (its rows [20, 410) hold more of the
@@ -1171,26 +966,6 @@ __global__ void __launch_bounds__(64) view_kernel(float *__restrict__ tab, int w
     }
 }
 
-// Host wait for the previous frame (its arena, tables and staging slots).
-int wait_frame(rtrt::DeviceState &st)
-{
-    hipError_t e = hipEventSynchronize(st.wf_done);
-    if (e != hipSuccess) return rtrt::fail_hip(e, "rtw frame wait");
-    st.wf_pending = false;
-    return RT_OK;
-}
-
-// Device slot of at least `bytes` that the previous frame may still read:
-// regrowing frees it, so wait for that frame first.
-int frame_scratch(rtrt::DeviceState &st, int slot, size_t bytes, void **out)
-{
-    if (st.cap[slot] < bytes && st.wf_pending) {
-        int rc = wait_frame(st);
-        if (rc) return rc;
-    }
-    return rtrt::scratch(st, slot, bytes, out);
-}
-
 // View tables for (w, h, ocl) in slot SLOT_VIEW, (re)computed on `s` only
 // when the frame size or semantics change (ordered after earlier frames by
 // the caller's wait on wf_done).
@@ -1198,7 +973,7 @@ int view_tables(rtrt::DeviceState &st, hipStream_t s, int w, int h, bool ocl, fl
                 const float **d_sx, const float **d_sy)
 {
     void *d = nullptr;
-    int rc = frame_scratch(st, rtrt::SLOT_VIEW, sizeof(float) * ((size_t)w + h), &d);
+    int rc = rtrt::frame_scratch(st, rtrt::SLOT_VIEW, sizeof(float) * ((size_t)w + h), &d);
     if (rc) return rc;
     if (st.vt_w != w || st.vt_h != h || st.vt_ocl != (int)ocl) {
         hipLaunchKernelGGL(view_kernel, dim3(1), dim3(64), 0, s, (float *)d, w, h, DX, DY, (int)ocl);
@@ -1230,30 +1005,24 @@ int wavefront_arena(rtrt::DeviceState &st, int slot, int w, int rows, int nsub, 
     const size_t TC = std::max<size_t>(P / 64, 1024);   // TIR list per level
     const size_t FC = std::max<size_t>(T / 16, 1024);   // fixup list
     const size_t FB = (T + 31) / 32 * 4;                // fixup bits
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t root_b = al(T * 16) + al(T * 4) + al((size_t)w * rows * 16) + al(T * 8) + al(FB) + al(FC * 4);
-    const size_t pool_b = al(P * 16) * 3 + al(P * 4) + al(P * 8);
-    const size_t bytes = al(sizeof(Scene)) + root_b + pool_b + (LEVELS - 1) * al(TC * 16) +
-                         al(sizeof(int) * C_TOTAL * CSTRIDE);
-    void *base = nullptr;
-    int rc = frame_scratch(st, slot, bytes, &base);
+    int rc = rtrt::carve_arena(st, slot, [&](rtrt::Arena &a) {
+        a.take(A->scene, sizeof(Scene));
+        a.take(A->rcol, T * 16);
+        a.take(A->rinfo, T * 4);
+        a.take(A->psum, (size_t)w * rows * 16);
+        a.take(A->rchild, T * 8);
+        a.take(A->fixbits, FB);
+        a.take(A->fixlist, FC * 4);
+        a.take(A->ia, P * 16);
+        a.take(A->ib, P * 16);
+        a.take(A->lcol, P * 16);
+        a.take(A->linfo, P * 4);
+        a.take(A->lchild, P * 8);
+        for (int L = 0; L < LEVELS - 1; L++) a.take(A->tir[L], TC * 16);
+        a.take(A->count, sizeof(int) * C_TOTAL * CSTRIDE);
+    });
     if (rc) return rc;
-    char *p = (char *)base;
-    auto take = [&](size_t b) { char *q = p; p += al(b); return q; };
-    A->scene = (const Scene *)take(sizeof(Scene));
-    A->rcol = (float4 *)take(T * 16);
-    A->rinfo = (int *)take(T * 4);
-    A->psum = (float4 *)take((size_t)w * rows * 16);
-    A->rchild = (int2 *)take(T * 8);
-    A->fixbits = (unsigned *)take(FB);
-    A->fixlist = (int *)take(FC * 4);
-    A->ia = (float4 *)take(P * 16);
-    A->ib = (float4 *)take(P * 16);
-    A->lcol = (float4 *)take(P * 16);
-    A->linfo = (int *)take(P * 4);
-    A->lchild = (int2 *)take(P * 8);
-    for (int L = 0; L < LEVELS; L++) A->tir[L] = L < LEVELS - 1 ? (int4 *)take(TC * 16) : nullptr;
-    A->count = (int *)take(sizeof(int) * C_TOTAL * CSTRIDE);
+    A->tir[LEVELS - 1] = nullptr;
     A->ovf = ovf;
     A->pool = (int)P;
     A->fixcap = (int)FC;
@@ -1264,23 +1033,12 @@ int wavefront_arena(rtrt::DeviceState &st, int slot, int w, int rows, int nsub, 
     return RT_OK;
 }
 
-// Resident blocks of a 256-thread kernel on this device (persistent grids).
-template <class K>
-int resident_blocks(K kernel)
-{
-    int dev = 0, cus = 0, per = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 1024;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 1024;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, 256, 0) != hipSuccess || per < 1) per = 1;
-    return cus * per;
-}
-
 template <bool COUNT>
 int launch_wavefront(const rt::whitted::WfArgs &A, int w, int rows, int row_end, const float *d_sx,
                      const float *d_sy, float DX, float DY, unsigned long long *cnt, hipStream_t s, uint32_t *d_xrgb)
 {
     using namespace rt::whitted;
-    static const int level_blocks = resident_blocks(level_kernel<COUNT>);
+    static const int level_blocks = rtrt::resident_blocks(level_kernel<COUNT>);
     const dim3 tiles((w + 15) / 16, (rows + 15) / 16), block(256);
     const int qblocks = (int)std::min<long long>(((long long)A.pool + 255) / 256, 2048);
     hipLaunchKernelGGL(root_kernel<COUNT>, tiles, block, 0, s, A, row_end, d_sx, d_sy, DX, DY, cnt);
@@ -1289,31 +1047,12 @@ int launch_wavefront(const rt::whitted::WfArgs &A, int w, int rows, int row_end,
         hipLaunchKernelGGL(level_kernel<COUNT>, dim3(level_blocks), block, 0, s, A, L, cnt);
     }
     hipLaunchKernelGGL(fixup_kernel<COUNT>, dim3(256), dim3(64), 0, s, A, d_sx, d_sy, DX, DY, cnt);
-    // Back-accumulation schedule (RT_WHITTED_BACKACC, A/B): 1 = a launch per
-    // level 4..1; 2 = levels (3 <- 4 <- 5), (1 <- 2 <- 3); 3 = (2 <- 3 <- 4 <- 5)
-    // and the final kernel folds 0 <- 1 <- 2; 4 = (3 <- 4 <- 5) and the final
-    // kernel folds 0 <- 1 <- 2 <- 3.
-    static const int backacc = [] {
-        const char *e = getenv("RT_WHITTED_BACKACC");
-        const int v = e ? atoi(e) : WF_BACKACC_LEVELS;
-        return v >= 1 && v <= 4 ? v : WF_BACKACC_LEVELS;
-    }();
-    static_assert(LEVELS == 6, "the back-accumulation schedules assume levels 0..5");
-    if (backacc == 1) {
-        for (int L = LEVELS - 2; L >= 1; L--)
-            hipLaunchKernelGGL(backacc_kernel<1>, dim3(qblocks), block, 0, s, A, L);
-        hipLaunchKernelGGL(final_kernel<1>, tiles, block, 0, s, A, row_end, d_xrgb);
-    } else if (backacc == 2) {
-        hipLaunchKernelGGL(backacc_kernel<2>, dim3(qblocks), block, 0, s, A, 3);
-        hipLaunchKernelGGL(backacc_kernel<2>, dim3(qblocks), block, 0, s, A, 1);
-        hipLaunchKernelGGL(final_kernel<1>, tiles, block, 0, s, A, row_end, d_xrgb);
-    } else if (backacc == 3) {
-        hipLaunchKernelGGL(backacc_kernel<3>, dim3(qblocks), block, 0, s, A, 2);
-        hipLaunchKernelGGL(final_kernel<2>, tiles, block, 0, s, A, row_end, d_xrgb);
-    } else {
-        hipLaunchKernelGGL(backacc_kernel<2>, dim3(qblocks), block, 0, s, A, 3);
-        hipLaunchKernelGGL(final_kernel<3>, tiles, block, 0, s, A, row_end, d_xrgb);
-    }
+    // Back-accumulation: levels (3 <- 4 <- 5), then (1 <- 2 <- 3); the final
+    // kernel folds 0 <- 1.
+    static_assert(LEVELS == 6, "the back-accumulation schedule assumes levels 0..5");
+    hipLaunchKernelGGL(backacc_kernel<2>, dim3(qblocks), block, 0, s, A, 3);
+    hipLaunchKernelGGL(backacc_kernel<2>, dim3(qblocks), block, 0, s, A, 1);
+    hipLaunchKernelGGL(final_kernel<1>, tiles, block, 0, s, A, row_end, d_xrgb);
     return rtrt::check_launch("rtw wavefront kernels");
 }
 
@@ -1325,12 +1064,8 @@ int render_async(const rt_primitive *d_prims, int nprims, uint32_t *d_xrgb, int 
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> lk(st->mu);
     hipStream_t s = (hipStream_t)stream;
-    // The arena and view tables belong to the device: order this frame after
-    // the previous one, whatever stream that ran on.
-    if (st->wf_pending) {
-        hipError_t e = hipStreamWaitEvent(s, st->wf_done, 0);
-        if (e != hipSuccess) return rtrt::fail_hip(e, "rtw_render_async wait");
-    }
+    rtrt::Frame frame(*st, s, "rtw_render_async");
+    if ((rc = frame.begin())) return rc;
     const float DX = (3.0f - -3.0f) / w, DY = (-2.25f - 2.25f) / h;    // Engine_InitRender / openCLcode.cl:20-21
     const float *d_sx, *d_sy;
     if ((rc = view_tables(*st, s, w, h, ocl, DX, DY, &d_sx, &d_sy))) return rc;
@@ -1371,8 +1106,6 @@ int render_async(const rt_primitive *d_prims, int nprims, uint32_t *d_xrgb, int 
     // 2 max(p, q) / (p + q) of a half arena (an A/B hook; the default is 1,1).
     int sp_p = 1, sp_q = 1;
     if (nstream == 2 && nslab == 2) {
-        sp_p = WF_SPLIT_P;
-        sp_q = WF_SPLIT_Q;
         if (const char *e = getenv("RT_WHITTED_SPLIT")) sscanf(e, "%d,%d", &sp_p, &sp_q);   // A/B
         sp_p = std::min(std::max(sp_p, 1), 64);
         sp_q = std::min(std::max(sp_q, 1), 64);
@@ -1384,21 +1117,12 @@ int render_async(const rt_primitive *d_prims, int nprims, uint32_t *d_xrgb, int 
     };
     const bool unequal = nstream == 2 && nslab == 2 && !(sp_p == 1 && sp_q == 1);
     const int slab_rows = unequal ? std::max(split_groups(0), split_groups(1)) * 16
-                                  : (int)((ngroups + nslab - 1) / nslab) * 16;
+                                  : rtrt::slab_rows(ngroups, 0, nslab);
     rt::whitted::WfArgs A[2];
-    hipStream_t ss[2] = {s, s};
-    if (nstream == 2) {
-        if ((rc = rtrt::aux_stream(*st))) return rc;
-        ss[1] = st->aux;
-        hipError_t e = hipEventRecord(st->fork_ev, s);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st->aux, st->fork_ev, 0);
-        if (e != hipSuccess) return rtrt::fail_hip(e, "rtw_render_async fork");
-    }
+    if (nstream == 2 && (rc = frame.fork())) return rc;
     unsigned long long *cnt = (unsigned long long *)d_counters;
-    // (after the fork, an error return still joins the second stream back)
-    const auto bail = [&](int code) { return nstream == 2 ? rtrt::join_aux_on_error(*st, s, code) : code; };
     for (int i = 0; i < nstream; i++) {
-        if ((rc = wavefront_arena(*st, i ? SLOT_WF2 : SLOT_WF, w, slab_rows, nsub, &A[i]))) return bail(rc);
+        if ((rc = wavefront_arena(*st, i ? SLOT_WF2 : SLOT_WF, w, slab_rows, nsub, &A[i]))) return frame.bail(rc);
         A[i].side = side;
         A[i].nsub = nsub;
         A[i].ocl = ocl;
@@ -1407,33 +1131,24 @@ int render_async(const rt_primitive *d_prims, int nprims, uint32_t *d_xrgb, int 
     }
     for (int k = 0; k < (int)nslab; k++) {
         rt::whitted::WfArgs &a = A[k % nstream];
-        hipStream_t sk = ss[k % nstream];
-        const int srows = unequal ? split_groups(k) * 16 : (int)((ngroups - k + nslab - 1) / nslab) * 16;
+        hipStream_t sk = frame.ss[k % nstream];
+        const int srows = unequal ? split_groups(k) * 16 : rtrt::slab_rows(ngroups, k, nslab);
         if (srows == 0) continue;                // (an unequal pair over fewer groups than its period)
         a.row_begin = row_begin + 16 * (unequal && k == 1 ? sp_p : k);
         a.npix = w * srows;
         a.ntrees = a.npix * nsub;
         // counters and tree flag words zeroed; the arena's scene image built by
         // its first slab (16-B words: the arena rounds every part to 256 B)
-        const auto words = [](size_t bytes) { return (int)((bytes + 15) / 16); };
-        const int nz0 = words(sizeof(int) * rt::whitted::C_TOTAL * rt::whitted::CSTRIDE);
-        const int nz1 = words(sizeof(unsigned) * (((size_t)a.ntrees + 31) / 32));
+        const int nz0 = rtrt::words16(sizeof(int) * rt::whitted::C_TOTAL * rt::whitted::CSTRIDE);
+        const int nz1 = rtrt::words16(sizeof(unsigned) * (((size_t)a.ntrees + 31) / 32));
         const int pblocks = std::min(1024, std::max(1, (nz0 + nz1 + 255) / 256));
         hipLaunchKernelGGL(rt::whitted::prep_kernel, dim3(pblocks), dim3(256), 0, sk, k < nstream ? d_prims : nullptr,
                            nprims, (rt::whitted::Scene *)a.scene, (uint4 *)a.count, nz0, (uint4 *)a.fixbits, nz1);
         rc = cnt ? launch_wavefront<true>(a, w, srows, row_end, d_sx, d_sy, DX, DY, cnt, sk, d_xrgb)
                  : launch_wavefront<false>(a, w, srows, row_end, d_sx, d_sy, DX, DY, cnt, sk, d_xrgb);
-        if (rc) return bail(rc);
+        if (rc) return frame.bail(rc);
     }
-    if (nstream == 2) {
-        hipError_t e = hipEventRecord(st->join_ev, st->aux);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s, st->join_ev, 0);
-        if (e != hipSuccess) return bail(rtrt::fail_hip(e, "rtw_render_async join"));
-    }
-    hipError_t e = hipEventRecord(st->wf_done, s);
-    if (e != hipSuccess) return rtrt::fail_hip(e, "rtw_render_async record");
-    st->wf_pending = true;
-    return RT_OK;
+    return frame.end();
 }
 
 }  // namespace
@@ -1469,31 +1184,10 @@ extern "C" int rtw_render_ocl(const rt_primitive *prims, int nprims, uint32_t *x
         if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0;
         return RT_OK;
     }
-    rtrt::DeviceState *st;
-    int rc = rtrt::state(&st);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lk(st->mu);
-    // slots 0..2 may still feed a frame issued on another stream
-    if (st->wf_pending && (rc = wait_frame(*st))) return rc;
-    const size_t frame_bytes = sizeof(uint32_t) * (size_t)w * h;
-    void *d_prims, *d_frame, *d_cnt;
-    if ((rc = rtrt::scratch(*st, 0, sizeof(rt_primitive) * nprims, &d_prims))) return rc;
-    if ((rc = rtrt::scratch(*st, 1, frame_bytes, &d_frame))) return rc;
-    if ((rc = rtrt::scratch(*st, 2, 4 * sizeof(uint64_t), &d_cnt))) return rc;
-    hipStream_t s = st->stream;
-    hipError_t e = hipMemcpyAsync(d_prims, prims, sizeof(rt_primitive) * nprims, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && counters) e = hipMemsetAsync(d_cnt, 0, 4 * sizeof(uint64_t), s);
-    if (e != hipSuccess) return rtrt::fail_hip(e, "rtw_render_ocl H2D");
-    rc = render_async((const rt_primitive *)d_prims, nprims, (uint32_t *)d_frame, w, h, 20, row_end,
-                      counters ? (uint64_t *)d_cnt : nullptr, s, true);
-    if (rc) return rc;
-    const size_t off = sizeof(uint32_t) * (size_t)20 * w, len = sizeof(uint32_t) * (size_t)(row_end - 20) * w;
-    e = hipMemcpyAsync((char *)xrgb + off, (char *)d_frame + off, len, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && counters)
-        e = hipMemcpyAsync(counters, d_cnt, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return rtrt::fail_hip(e, "rtw_render_ocl D2H");
-    return RT_OK;
+    return rtrt::render_blocking("rtw_render_ocl", prims, nprims, xrgb, w, h, 20, row_end, counters,
+                                 [&](const rt_primitive *d_prims, uint32_t *d_frame, uint64_t *d_cnt, hipStream_t s) {
+                                     return render_async(d_prims, nprims, d_frame, w, h, 20, row_end, d_cnt, s, true);
+                                 });
 }
 
 extern "C" int rtw_render(const rt_primitive *prims, int nprims, uint32_t *xrgb, int w, int h,
@@ -1503,33 +1197,9 @@ extern "C" int rtw_render(const rt_primitive *prims, int nprims, uint32_t *xrgb,
         return rtrt::fail(RT_ERR_INVALID, "rtw_render: bad arguments");
     if (row_begin < 20 || row_end > h || row_begin >= row_end)
         return rtrt::fail(RT_ERR_INVALID, "rtw_render: rows must satisfy 20 <= row_begin < row_end <= h");
-    rtrt::DeviceState *st;
-    int rc = rtrt::state(&st);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lk(st->mu);
-    // slots 0..2 may still feed a frame issued on another stream
-    if (st->wf_pending && (rc = wait_frame(*st))) return rc;
-    const size_t frame_bytes = sizeof(uint32_t) * (size_t)w * h;
-    void *d_prims, *d_frame, *d_cnt;
-    if ((rc = rtrt::scratch(*st, 0, sizeof(rt_primitive) * nprims, &d_prims))) return rc;
-    if ((rc = rtrt::scratch(*st, 1, frame_bytes, &d_frame))) return rc;
-    if ((rc = rtrt::scratch(*st, 2, 4 * sizeof(uint64_t), &d_cnt))) return rc;
-    hipStream_t s = st->stream;
-    hipError_t e = hipMemcpyAsync(d_prims, prims, sizeof(rt_primitive) * nprims, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return rtrt::fail_hip(e, "rtw_render H2D prims");
-    // Rows outside [row_begin,row_end) are left untouched: copy only the window back.
-    if (counters && (e = hipMemsetAsync(d_cnt, 0, 4 * sizeof(uint64_t), s)) != hipSuccess)
-        return rtrt::fail_hip(e, "rtw_render memset");
-    rc = rtw_render_async((const rt_primitive *)d_prims, nprims, (uint32_t *)d_frame, w, h, row_begin,
-                          row_end, counters ? (uint64_t *)d_cnt : nullptr, s);
-    if (rc) return rc;
-    const size_t off = sizeof(uint32_t) * (size_t)row_begin * w;
-    const size_t len = sizeof(uint32_t) * (size_t)(row_end - row_begin) * w;
-    e = hipMemcpyAsync((char *)xrgb + off, (char *)d_frame + off, len, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return rtrt::fail_hip(e, "rtw_render D2H frame");
-    if (counters && (e = hipMemcpyAsync(counters, d_cnt, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
-        return rtrt::fail_hip(e, "rtw_render D2H counters");
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return rtrt::fail_hip(e, "rtw_render sync");
-    return RT_OK;
+    return rtrt::render_blocking("rtw_render", prims, nprims, xrgb, w, h, row_begin, row_end, counters,
+                                 [&](const rt_primitive *d_prims, uint32_t *d_frame, uint64_t *d_cnt, hipStream_t s) {
+                                     return render_async(d_prims, nprims, d_frame, w, h, row_begin, row_end, d_cnt, s,
+                                                         false);
+                                 });
 }
