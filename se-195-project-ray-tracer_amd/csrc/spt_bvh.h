@@ -1,12 +1,12 @@
 // spt_bvh.h -- host-side builders of smallpt's exact-culling sphere
-// hierarchies (scenes of >= 256 spheres; the device walks are in smallpt.hip).
+// hierarchies (scenes of >= 256 spheres; the device walks are in spt_walk.h).
 // Host-only C++ (no HIP types): smallpt.hip uploads what these build, and
 // tests/native/libspt_bvh_check.so runs the same builders on the CPU to check
 // their invariants against a scalar restatement of the device walk.
 //
 // The reference tests every sphere for every ray (smallptgpu-v1.6/
 // geomfunc.h:71-110).  A hierarchy only skips spheres whose float
-// SphereIntersect distance provably cannot be taken; smallpt.hip's "Skipping
+// SphereIntersect distance provably cannot be taken; spt_walk.h's "Skipping
 // rule" comment gives the margin argument.  Two layouts are built:
 //   * BvhBuild: binned-SAH binary tree (64 bins), leaves of <= 4 spheres, eight
 //     depth-first layouts (one per ray-direction octant, near child first)
@@ -30,7 +30,7 @@ namespace sptbvh {
 
 struct f4 { float x, y, z, w; };
 
-constexpr float ALPHA_R = 1.f / 64.f;   // margin per unit of a box's half diagonal (smallpt.hip)
+constexpr float ALPHA_R = 1.f / 64.f;   // margin per unit of a box's half diagonal (spt_walk.h)
 constexpr int LEAF = 4;                  // spheres per leaf
 constexpr int MIN_SPHERES = 256;         // scenes below this are scanned in full
 constexpr int MAX_ALWAYS = 16;           // spheres tested outside the hierarchy (radius > 64 x median)

@@ -1,6 +1,6 @@
 // spt_bvh_check.cpp -- test-only CPU checks of smallpt's hierarchy builders
 // (csrc/spt_bvh.h): the 8-wide tree's structure, and a scalar restatement of
-// the device walk (smallpt.hip's wide_visit / bvh_walk_wide, minus the wave
+// the device walk (spt_walk.h's wide_visit / bvh_walk_wide, minus the wave
 // scheduling) compared with the reference's full scan (geomfunc.h:71-110:
 // every sphere, i descending, update iff d != 0 && d < t) ray by ray.
 // Built with -ffp-contract=off: the sphere test is the reference's float

@@ -1,5 +1,5 @@
 """Empirical check of the error bound behind the sphere hierarchy's culling
-margin (smallpt.hip, BvhView comment): the point at the float32
+margin (spt_walk.h, BvhView comment): the point at the float32
 SphereIntersect distance t (geomfunc.h:32-59 arithmetic, no FMA) of a
 vnorm-normalised direction d, |d|^2 = 1 + e, lies within
 1.04e-3 * max(|op|, r) + sqrt(e) * t of the sphere -- the analytical bound,

@@ -1,5 +1,5 @@
 """CPU checks of the 8-wide hierarchy (csrc/spt_bvh.h WideBuild) through a
-scalar restatement of smallpt.hip's wide walk (tests/native/spt_bvh_check.cpp):
+scalar restatement of spt_walk.h's wide walk (tests/native/spt_bvh_check.cpp):
 for every ray, the walk's nearest hit (distance bits and sphere index, ties to
 the highest index) or any-hit occluder (the highest index, as the counted
 kernel reports IntersectP's position) equals the reference's full scan
