@@ -17,9 +17,9 @@
 //     immediately starts its next sample, so a wave's cost is the max over
 //     lanes of the total bounces of nsamples paths (~ the mean for spp >> 1),
 //     not the sum over samples of the per-sample max;
-//   * RNG state, the colour accumulator and the path state stay in VGPRs for
-//     the whole launch: HBM traffic is 32 B per pixel per launch, whatever
-//     nsamples is;
+//   * RNG state and the path state stay in VGPRs for the whole launch, the
+//     colour accumulator (touched once per sample) in a lane-private LDS
+//     area: HBM traffic is 32 B per pixel per launch, whatever nsamples is;
 //   * spheres are staged once per block into LDS as SoA float4 (centre,
 //     rad^2) + material records and read with wave-uniform indices (LDS
 //     broadcast); scenes larger than the LDS budget are read from global
@@ -281,7 +281,12 @@ __device__ __forceinline__ int to_int(float x)
 // SIMD; every bound measured against its neighbours):
 //   full-scan one-query kernels: unbounded (1);
 //   the uncounted two-query kernel (DUAL): 7 -- 85 -> 72 VGPRs, no VGPR
-//     spills, occupancy 5 -> 7: Cornell 1080p 17.87 -> 17.3 ms;
+//     spills, occupancy 5 -> 7: Cornell 1080p 17.87 -> 17.3 ms.  8 measured
+//     without scratch (colour, coordinates and camera terms parked: 64
+//     VGPRs, private segment 0) and not kept: 8 waves cap the kernel at 80
+//     SGPRs, the rest go through v_readlane in every iteration (+1.05 % VALU
+//     instructions), and the eighth wave buys no rate: 16.98 ms against
+//     16.57 ms for the same code at 7 (profiles/r07);
 //   binary-hierarchy (GEO_BVH) kernels: 6 -- 93 -> 80 VGPRs (2 spilled): the
 //     latency-bound walk gains more from the sixth wave than the spills cost;
 //   8-wide (GEO_WIDE) kernels: 4 -- 126 VGPRs unbounded; 5 or 6 spill;
@@ -289,6 +294,9 @@ __device__ __forceinline__ int to_int(float x)
 constexpr int SPT_MINWAVES = 1, SPT_DUAL_MINWAVES = 7, BVH_MINWAVES = 6, WIDE_MINWAVES = 4, BVH_MINWAVES_COUNT = 4;
 constexpr int GEO_LDS = 0, GEO_GLOBAL = 1, GEO_BVH = 2, GEO_WIDE = 3;
 constexpr int GS_BYTES = 6160;      // GEO_BVH group staging strip: 8 x 96 colour floats, 8 x 64 seed words, 8 x 32 pixels, count
+constexpr int PARK_SLOTS = 3;       // full-scan kernels' parked per-lane state: the running-average colour
+constexpr int PARK_BYTES_PER_WAVE = PARK_SLOTS * 64 * 4;
+constexpr int PARK_HEAD_BYTES = 64;  //   and, before the waves' areas, the block's copy of the camera terms
 
 // DUAL (path tracing, full-scan geometry, scenes with exactly one light): a
 // DIFF vertex builds its light sample's shadow ray AND its bounce ray in the
@@ -324,9 +332,37 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
     // until the window is done, so a block's LDS copy of the hierarchy is
     // made once and a CU never idles behind one block's slowest wave.
     constexpr bool PERSIST = GEO == GEO_WIDE;
+    // PARK (full-scan kernels): state that is touched once per sample or
+    // once per pass B, not in the sphere loop, lives in LDS after the scene
+    // copy instead of in registers.  The running-average colour sits in a
+    // lane-private area (per wave PARK_SLOTS x 64 dwords, dword slot * 64 +
+    // lane: every access is conflict-free; only the lane itself ever reads or
+    // writes its dwords, so no barrier is needed); the camera terms sit
+    // once per block before it.  Arithmetic, draws and stores are unchanged.
+    constexpr bool PARK = GEO == GEO_LDS || GEO == GEO_GLOBAL;
     // Dynamic LDS carve (16-B multiples): geo | emi | col (n each) | lrec (3 per light),
-    // a copy of the scene's global SoA (spt_scene_create).
+    // a copy of the scene's global SoA (spt_scene_create); PARK: then the
+    // parking area, PARK_HEAD_BYTES and PARK_BYTES_PER_WAVE per wave of the block.
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int park_off = (PARK && LDS) ? 16 * (3 * nspheres + 3 * (nlights > 0 ? nlights : 1)) : 0;
+    // (the thread index is re-read behind an empty asm at every use: hoisted
+    // out of the loop, the address would be carried in a register of its own)
+    const auto park_ptr = [&]() {
+        int t = (int)threadIdx.x;
+        asm volatile("" : "+v"(t));
+        return (float *)(smem + park_off + PARK_HEAD_BYTES) + (t >> 6) * (PARK_SLOTS * 64) + (t & 63);
+    };
+    // The camera terms of pass B (twelve floats, with 1 / w and 1 / h) head
+    // the parking area: read there by every lane at one address (broadcast)
+    // instead of being held in fourteen scalar registers for the whole loop.
+    if (PARK && threadIdx.x == 0) {
+        float4 *pc = (float4 *)(smem + park_off);
+        pc[0] = make_float4(cam.x.x, cam.x.y, cam.x.z, 1.f / w);           // smallptCPU.cpp:80-81
+        pc[1] = make_float4(cam.y.x, cam.y.y, cam.y.z, 1.f / h);
+        pc[2] = make_float4(cam.dir.x, cam.dir.y, cam.dir.z, 0.f);
+        pc[3] = make_float4(cam.orig.x, cam.orig.y, cam.orig.z, 0.f);
+    }
+    if (PARK && !LDS) __syncthreads();
     Scene S;
     if (LDS) {
         float4 *s = (float4 *)smem;
@@ -488,6 +524,12 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
             if (first_sample > 0)
                 col = mk(colors[3 * (size_t)i], colors[3 * (size_t)i + 1], colors[3 * (size_t)i + 2]);
         }
+        if (PARK && first_sample > 0) {         // (first_sample == 0: the first sample overwrites it)
+            float *p = park_ptr();
+            p[0] = col.x;
+            p[64] = col.y;
+            p[128] = col.z;
+        }
         const float invW = 1.f / w, invH = 1.f / h;             // :80-81
         // Refill state: the lane's pixel is px_ok (its group pgrp, started at
         // pix_t0), exhausted once the window has no pixel left for it; the
@@ -620,11 +662,21 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                 const v3 a = (fabsf(wv.x) > .1f) ? mk(0.f, 1.f, 0.f) : mk(1.f, 0.f, 0.f);
                 const v3 cu = vxcross(a, wv);
                 // camera: r1 = x1 - .5, r2 = x2 - .5
-                const float kcx = (x + __builtin_fmaf(f1, .5f, -1.5f)) * invW - .5f;   // r1 = GetRandom() - .5f
-                const float kcy = (y + __builtin_fmaf(f2, .5f, -1.5f)) * invH - .5f;
-                const v3 rdir = mk(cam.x.x * kcx + cam.y.x * kcy + cam.dir.x,
-                                   cam.x.y * kcx + cam.y.y * kcy + cam.dir.y,
-                                   cam.x.z * kcx + cam.y.z * kcy + cam.dir.z);
+                // (PARK: the camera terms from the parking area's head)
+                float4 cmx = make_float4(cam.x.x, cam.x.y, cam.x.z, invW), cmy = make_float4(cam.y.x, cam.y.y, cam.y.z, invH);
+                float4 cmd = make_float4(cam.dir.x, cam.dir.y, cam.dir.z, 0.f);
+                float4 cmo = make_float4(cam.orig.x, cam.orig.y, cam.orig.z, 0.f);
+                if constexpr (PARK) {
+                    int o = park_off;
+                    asm volatile("" : "+s"(o));
+                    const float4 *pc = (const float4 *)(smem + o);
+                    cmx = pc[0]; cmy = pc[1]; cmd = pc[2]; cmo = pc[3];
+                }
+                const float kcx = (x + __builtin_fmaf(f1, .5f, -1.5f)) * cmx.w - .5f;   // r1 = GetRandom() - .5f
+                const float kcy = (y + __builtin_fmaf(f2, .5f, -1.5f)) * cmy.w - .5f;
+                const v3 rdir = mk(cmx.x * kcx + cmy.x * kcy + cmd.x,
+                                   cmx.y * kcx + cmy.y * kcy + cmd.y,
+                                   cmx.z * kcx + cmy.z * kcy + cmd.z);
                 const v3 vn = vnorm(need_bounce ? cu : rdir);
                 if (need_bounce) {
                     const float r1 = 2.f * PI_F * x1;
@@ -638,7 +690,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                     ray.d = nd;                          // origin: hit
                 } else {
                     v3 rorig = vsmul(0.1f, rdir);
-                    rorig = vadd(rorig, mk(cam.orig.x, cam.orig.y, cam.orig.z));
+                    rorig = vadd(rorig, mk(cmo.x, cmo.y, cmo.z));
                     ray.o = rorig;
                     ray.d = vn;
                     // (rad, thr, depth, specular were reset when the previous
@@ -938,7 +990,21 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
             if (done) {                                         // :110-118 running average
                 SPT_PROF(PB_DONE);
                 const int current = first_sample + k;
-                if (current == 0) {
+                if constexpr (PARK) {
+                    // the same average on the parked colour: loaded, updated and written back here
+                    float *p = park_ptr();
+                    v3 c = rad;
+                    if (current != 0) {
+                        const float k1 = (float)current;
+                        const float k2 = rcp_nr(k1 + 1.f);
+                        c.x = (p[0] * k1 + rad.x) * k2;
+                        c.y = (p[64] * k1 + rad.y) * k2;
+                        c.z = (p[128] * k1 + rad.z) * k2;
+                    }
+                    p[0] = c.x;
+                    p[64] = c.y;
+                    p[128] = c.z;
+                } else if (current == 0) {
                     col = rad;
                 } else {
                     const float k1 = (float)current;
@@ -975,6 +1041,10 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
             gs_seed[r * 64 + 2 * c] = s0;
             gs_seed[r * 64 + 2 * c + 1] = s1;
         } else if (lead && !refill) {            // (refill: stored as each pixel finished)
+            if (PARK && nsamples > 0) {          // the parked colour back
+                const float *p = park_ptr();
+                col = mk(p[0], p[64], p[128]);
+            }
             if (nsamples > 0) {
                 colors[3 * (size_t)i] = col.x;
                 colors[3 * (size_t)i + 1] = col.y;
@@ -1293,6 +1363,9 @@ int launch(const spt_scene &sc, const RenderCall &c, const Shape &g)
     const float4 *gg = sc.d_soa, *ge = gg + n, *gc = ge + n, *gl = gc + n;
     size_t lds = geo == GEO_LDS ? (size_t)(3 * n + 3 * std::max(sc.nlights, 1)) * sizeof(float4) : 0;
     if (geo == GEO_BVH) lds = (size_t)(g.wpb / 4) * GS_BYTES;
+    // full-scan kernels: the parked per-lane state, after the scene copy (the
+    // 16-wave shape's reservation below covers it unless the scene is large)
+    if (geo == GEO_LDS || geo == GEO_GLOBAL) lds += PARK_HEAD_BYTES + (size_t)g.wpb * PARK_BYTES_PER_WAVE;
     if (g.wpb == 16 && lds < 81 * 1024) lds = 81 * 1024;   // > half the CU's 160 KiB: one block per CU
     int *work = nullptr;
     if (geo == GEO_WIDE) {
