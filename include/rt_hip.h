@@ -188,6 +188,31 @@ int spt_render_async(const rt_sphere *d_spheres, unsigned nspheres, const rt_cam
 typedef struct spt_scene spt_scene;
 int spt_scene_create(const rt_sphere *spheres, unsigned nspheres, spt_scene **out);
 int spt_scene_destroy(spt_scene *scene);
+/* A read-only description of a prepared scene and of the most recent launch
+ * on it, for tests and tools: fills out[0 .. min(nout, SPT_INFO_WORDS)).
+ * Host bookkeeping only -- no device work, no synchronisation; the launch
+ * words are written by the thread that launches.  The scene's words:
+ *   [0] kernel family: SPT_GEO_LDS (the scene staged in LDS, full scan),
+ *       SPT_GEO_GLOBAL (full scan from global memory), SPT_GEO_BVH (binary
+ *       hierarchy walked from global memory), SPT_GEO_WIDE (8-wide hierarchy
+ *       in LDS)
+ *   [1] spheres   [2] lights (emitters)
+ *   [3] spheres tested outside the hierarchy (radius > 64 x the median, <= 16)
+ *   [4] binary hierarchy nodes   [5] 8-wide nodes   [6] 8-wide levels
+ *   [7] the 8-wide tree's leaf size, 8, 12 or 16 (0: no 8-wide tree)
+ *   [8] 1 if no sphere takes the refraction branch
+ * The most recent launch's words (all 0 before the first):
+ *   [9] launches so far   [10] waves per block   [11] blocks
+ *   [12] lanes per pixel of the cooperative tier, 8, 4 or 2 (0: none)
+ *   [13] cooperative (tier-1) tiles   [14] routed (tier-2) tiles
+ *   [15] 1 if the two-query iteration ran   [16] dynamic LDS bytes per block */
+#define SPT_GEO_LDS 0
+#define SPT_GEO_GLOBAL 1
+#define SPT_GEO_BVH 2
+#define SPT_GEO_WIDE 3
+#define SPT_INFO_WORDS 17
+int spt_scene_info(const spt_scene *scene, int *out, int nout);
+
 /* spt_render_async on a prepared scene: asynchronous on `stream`
  * (graph-capturable).  Hierarchy scenes (>= 256 spheres) learn a dispatch
  * order: the first launch of a (window, camera, nsamples, mode) key records

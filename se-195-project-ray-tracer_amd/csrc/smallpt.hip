@@ -1251,14 +1251,14 @@ struct spt_scene {
     mutable sptsched::SptSched sched_cnt;   //   ... of the full-counter launches (their own tile costs)
     mutable sptsched::WorkRing work;  // work counters of the persistent (8-wide hierarchy) launches
     bool no_refr = false;             // no sphere has refl == REFR (render_kernel's sflags)
+    int leaf_max = 0;                 // the 8-wide tree's leaf size (sptbvh::choose_wide; 0: no wide tree)
+    // The most recent launch (written on the host by launch(), read by spt_scene_info).
+    struct LastLaunch { int count = 0, wpb = 0, nblocks = 0, cg = 0, n1 = 0, n2 = 0, dual = 0, lds = 0; };
+    mutable LastLaunch last;
 };
 
 namespace {
-constexpr size_t WIDE_LDS_MAX = 144 * 1024;
-size_t wide_lds_bytes(int wnodes, int wdepth, int wpb, bool counted = true)
-{
-    return (size_t)(counted ? 144 : 112) * wnodes + (size_t)wpb * 256 * (wdepth > 1 ? wdepth - 1 : 1);
-}
+using sptbvh::wide_lds_bytes;
 
 // One render call, as the entry points receive it: rows [r0, r1) (every
 // gstride-th 8-row group), or (list) the caller's nlist tile groups over the
@@ -1289,6 +1289,8 @@ int counter_mode(const RenderCall &c)
 int scene_geo(const spt_scene &sc)
 {
     using namespace rt::smallpt;
+    static_assert(GEO_LDS == SPT_GEO_LDS && GEO_GLOBAL == SPT_GEO_GLOBAL && GEO_BVH == SPT_GEO_BVH &&
+                  GEO_WIDE == SPT_GEO_WIDE, "rt_hip.h's family codes (spt_scene_info)");
     if (sc.bvh.wnode) return GEO_WIDE;
     if (sc.bvh.node) return GEO_BVH;
     const size_t bytes = (size_t)(3 * sc.n + 3 * std::max(sc.nlights, 1)) * sizeof(float4);
@@ -1330,11 +1332,9 @@ Kernel pick_mode(bool dl, int cmode, bool dual, int cg)
     return pick_counted<GEO, false, false>(cmode, cg);
 }
 
-// dual: the scene has exactly one light; cg: lanes per pixel of the launch's
-// cooperative tier (8-wide kernels; 0: none -- the kernel carries the
-// cooperative walk only when the launch has such a tier, and only the group
-// size it uses).
-Kernel pick_kernel(int geo, bool dl, int cmode, bool dual, int cg)
+// Whether a launch runs the two-query iteration (one_light: the scene has
+// exactly one light).
+bool two_query_form(int geo, bool dl, bool one_light)
 {
     // The two-query iteration for path tracing in single-light scenes, at
     // every launch shape: one iteration per lit DIFF vertex instead of two.
@@ -1345,7 +1345,16 @@ Kernel pick_kernel(int geo, bool dl, int cmode, bool dual, int cg)
     // (The hierarchy walks keep the one-query form: their two resumable
     // walks in one loop spill)
     const int dual_env = getenv("RT_SPT_DUAL") ? atoi(getenv("RT_SPT_DUAL")) : -1;
-    dual = dual && dual_env != 0;
+    using namespace rt::smallpt;
+    return one_light && dual_env != 0 && !dl && (geo == GEO_LDS || geo == GEO_GLOBAL);
+}
+
+// dual: two_query_form's answer; cg: lanes per pixel of the launch's
+// cooperative tier (8-wide kernels; 0: none -- the kernel carries the
+// cooperative walk only when the launch has such a tier, and only the group
+// size it uses).
+Kernel pick_kernel(int geo, bool dl, int cmode, bool dual, int cg)
+{
     using namespace rt::smallpt;
     if (geo == GEO_WIDE) return pick_mode<GEO_WIDE>(dl, cmode, dual, cg);
     if (geo == GEO_BVH) return pick_mode<GEO_BVH>(dl, cmode, dual, cg);
@@ -1374,7 +1383,9 @@ int launch(const spt_scene &sc, const RenderCall &c, const Shape &g)
             return rtrt::check_launch("spt work counters") ? RT_ERR_HIP : RT_ERR_INVALID;
     }
     const sptpolicy::Tiers t = sptpolicy::heavy_tiers(g, sc.cus);
-    const Kernel kern = pick_kernel(geo, dl, cmode, sc.nlights == 1, t.cg);
+    const bool dual = two_query_form(geo, dl, sc.nlights == 1);
+    const Kernel kern = pick_kernel(geo, dl, cmode, dual, t.cg);
+    sc.last = {sc.last.count + 1, g.wpb, g.nblocks, t.cg, t.n1, t.n2, dual ? 1 : 0, (int)lds};
     hipLaunchKernelGGL(kern, dim3(g.nblocks), dim3(64 * g.wpb), lds, c.stream, sc.d_spheres, n, *c.cam, c.colors,
                        c.seeds_in, c.seeds_out, c.pixels, c.w, c.h, c.r0, c.r1, g.tiles_x, g.ntiles, g.nslots,
                        g.gstride, c.first_sample, c.nsamples, sptpolicy::prio_schedule(g), g.order, g.cost, gg, ge, gc,
@@ -1406,15 +1417,9 @@ int build_scene_bvh(spt_scene *sc, const rt_sphere *spheres)
         nodes.insert(nodes.end(), lay.begin(), lay.end());
     }
     sptbvh::WideBuild wb;
-    bool wide = false;
     const char *we = getenv("RT_SPT_WIDE");             // 0: the binary walk only (A/B, tests)
-    if (nn && !(we && atoi(we) == 0)) {
-        for (int lm : {8, 12, 16}) {    // (leaves of <= 5 or 6: slower, profiles/r03/c4_leaf_size_ab.log)
-            wb.leaf_max = lm;
-            wb.build(b);
-            if (wide_lds_bytes(wb.nnodes, wb.depth, sptpolicy::WIDE_WPB) <= WIDE_LDS_MAX) { wide = true; break; }
-        }
-    }
+    if (!(we && atoi(we) == 0)) sc->leaf_max = sptbvh::choose_wide(b, wb, sptpolicy::WIDE_WPB);
+    const bool wide = sc->leaf_max != 0;
     std::vector<float4> geo(nb + na);
     std::vector<int> ids(nb + na);
     for (int j = 0; j < nb + na; j++) {
@@ -1545,6 +1550,17 @@ extern "C" int spt_scene_destroy(spt_scene *sc)
     sptsched::sched_release(sc->sched);
     sptsched::sched_release(sc->sched_cnt);
     delete sc;
+    return RT_OK;
+}
+
+extern "C" int spt_scene_info(const spt_scene *sc, int *out, int nout)
+{
+    if (!sc || !out || nout < 1) return rtrt::fail(RT_ERR_INVALID, "spt_scene_info: bad arguments");
+    const spt_scene::LastLaunch &l = sc->last;
+    const int v[SPT_INFO_WORDS] = {scene_geo(*sc), sc->n, sc->nlights, sc->bvh.nalways, sc->bvh.nnodes,
+                                   sc->bvh.wnodes, sc->bvh.wdepth, sc->leaf_max, sc->no_refr ? 1 : 0, l.count,
+                                   l.wpb, l.nblocks, l.cg, l.n1, l.n2, l.dual, l.lds};
+    std::copy(v, v + std::min(nout, (int)SPT_INFO_WORDS), out);
     return RT_OK;
 }
 

@@ -383,6 +383,33 @@ struct WideBuild {
     }
 };
 
+// ---------------------------------------------------------------------------
+// The wide layout a scene gets.  A block of wpb waves stages the nodes in LDS
+// (112 B each, plus 32 B of per-slot highest indices for the counted any-hit
+// walk) and keeps one 256-B stack level per wave and level below the root;
+// the budget leaves a CU's 160 KiB room for that one block.
+constexpr size_t WIDE_LDS_MAX = 144 * 1024;
+inline size_t wide_lds_bytes(int wnodes, int wdepth, int wpb, bool counted = true)
+{
+    return (size_t)(counted ? 144 : 112) * wnodes + (size_t)wpb * 256 * (wdepth > 1 ? wdepth - 1 : 1);
+}
+
+// Builds into wb the 8-wide tree of b with the smallest leaf size in {8, 12,
+// 16} that fits WIDE_LDS_MAX for blocks of wpb waves, and returns that leaf
+// size; 0 when none fits (wb then holds the leaf-16 tree, not to be used) or
+// b is empty: such a scene walks the binary tree from global memory.
+// (Leaves of <= 5 or 6: slower, profiles/r03/c4_leaf_size_ab.log.)
+inline int choose_wide(const BvhBuild &b, WideBuild &wb, int wpb)
+{
+    if (b.nodes.empty()) return 0;
+    for (int lm : {8, 12, 16}) {
+        wb.leaf_max = lm;
+        wb.build(b);
+        if (wide_lds_bytes(wb.nnodes, wb.depth, wpb) <= WIDE_LDS_MAX) return lm;
+    }
+    return 0;
+}
+
 }  // namespace sptbvh
 
 #endif

@@ -119,6 +119,22 @@ class SmallptScene:
         check(lib().spt_scene_create(C.addressof(spheres), nspheres, C.byref(self.handle)))
         self.n = nspheres
 
+    # spt_scene_info's words in order (include/rt_hip.h); "family" is one of FAMILIES
+    FAMILIES = ("GEO_LDS", "GEO_GLOBAL", "GEO_BVH", "GEO_WIDE")
+    INFO = ("family", "nspheres", "nlights", "nalways", "nodes", "wnodes", "wdepth", "leaf_max", "no_refr",
+            "launches", "wpb", "nblocks", "cg", "n1", "n2", "two_query", "lds_bytes")
+
+    def info(self):
+        """The scene's kernel family and hierarchy layout, and the shape and
+        tiers of the most recent launch on it (spt_scene_info): a dict keyed
+        by INFO.  Host bookkeeping only, no device work."""
+        out = (C.c_int * len(self.INFO))()
+        check(lib().spt_scene_info(self.handle, out, len(out)))
+        d = dict(zip(self.INFO, out))
+        d["family"] = self.FAMILIES[d["family"]]
+        d["no_refr"], d["two_query"] = bool(d["no_refr"]), bool(d["two_query"])
+        return d
+
     def close(self):
         if self.handle:
             lib().spt_scene_destroy(self.handle)

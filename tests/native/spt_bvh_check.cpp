@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <vector>
 #include "spt_bvh.h"
+#include "spt_policy.h"
 
 namespace {
 
@@ -216,6 +217,38 @@ int spt_bvh_wide_stats(const rt_sphere *sp, int n, long long *out)
     out[3] = (long long)P.always.size();
     out[4] = (long long)P.wide.words.size() * 4;
     return 0;
+}
+
+// The wide layout the library picks for a scene (sptbvh::choose_wide, the
+// rule build_scene_bvh runs).  out[0..4]: the chosen leaf size (0: no wide
+// tree fits, the scene walks the binary tree), its wide nodes, wide depth,
+// always spheres, LDS bytes of a counted launch; out[5 + 3k ..]: wide nodes,
+// depth and LDS bytes at leaf size 8, 12, 16 (k = 0, 1, 2).  Returns the
+// chosen leaf size.
+int spt_bvh_wide_choice(const rt_sphere *sp, int n, long long *out)
+{
+    std::vector<int> always;
+    sptbvh::BvhBuild b2;
+    sptbvh::partition_and_build(sp, n, always, b2);
+    const int wpb = sptpolicy::WIDE_WPB;
+    int k = 0;
+    for (int lm : {8, 12, 16}) {
+        sptbvh::WideBuild w;
+        w.leaf_max = lm;
+        w.build(b2);
+        out[5 + 3 * k] = w.nnodes;
+        out[6 + 3 * k] = w.depth;
+        out[7 + 3 * k] = (long long)sptbvh::wide_lds_bytes(w.nnodes, w.depth, wpb);
+        k++;
+    }
+    sptbvh::WideBuild wide;
+    const int lm = sptbvh::choose_wide(b2, wide, wpb);
+    out[0] = lm;
+    out[1] = lm ? wide.nnodes : 0;
+    out[2] = lm ? wide.depth : 0;
+    out[3] = (long long)always.size();
+    out[4] = lm ? (long long)sptbvh::wide_lds_bytes(wide.nnodes, wide.depth, wpb) : 0;
+    return lm;
 }
 
 // Rays (o.xyz, d.xyz) x nrays; shadow rays use maxt[r] (NULL: nearest hit).

@@ -1,0 +1,351 @@
+"""GPU parity of smallpt's hierarchy kernels at the layouts a scene picks on
+its own (tests/scenes_layouts.py): 8-wide trees with leaves of 12 and 16
+spheres, the binary walk a scene falls back to when no 8-wide tree fits, the
+cooperative walks (eight, four and two lanes per pixel) on scenes with SPEC
+and REFR spheres, several lights and direct lighting, the edges of the
+always / tree partition, and frames smaller than one block.
+
+The reference is always the oracle's full scan (oracle.smallpt_render, the
+restatement of Intersect / IntersectP), computed once per (scene, frame,
+mode); every comparison is bit for bit -- HDR colours, seeds, pixels, and all
+four counters of a counted launch.  Every case first asserts through
+spt_scene_info (SmallptScene.info) the kernel family, leaf size and tier it
+means to run, so none can pass on another path."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import scenes_layouts as sl
+
+pytestmark = pytest.mark.gpu
+
+SPP = 2
+MODES = [pytest.param(0, id="pt"), pytest.param(1, id="dl")]
+FRAME = (64, 48)        # 24 tiles in six groups: one persistent block
+
+
+@pytest.fixture(scope="module")
+def world(oracle):
+    """Scenes (built once) and oracle frames (computed once per scene, frame,
+    window and mode; read-only)."""
+    scenes, frames = {}, {}
+
+    def scene(name):
+        if name not in scenes:
+            if name in sl.LAYOUT_SCENES:
+                S, n = sl.cloud(sl.LAYOUT_SCENES[name][0])
+                cam = sl.cloud_camera
+            elif name == "n255":
+                (S, n), cam = sl.n255(), sl.small_camera
+            elif name == "cornell":
+                import rtamd
+                (S, n), cam = rtamd.scenes.cornell(), rtamd.scenes.cornell_camera
+            else:
+                make, cam = sl.EDGE_SCENES[name]
+                S, n = make()
+            scenes[name] = (S, n, cam)
+        return scenes[name]
+
+    def ref(name, w, h, mode, rows=None):
+        key = (name, w, h, mode, rows)
+        if key not in frames:
+            S, n, cam = scene(name)
+            col = np.zeros(3 * w * h, np.float32)
+            seeds = oracle.seeds(w, h)
+            px = np.zeros(w * h, np.uint32)
+            r0, r1 = rows or (0, h)
+            cnt = oracle.smallpt_render(S, n, cam(w, h), col, seeds, px, w, h, 0, SPP, row_begin=r0, row_end=r1,
+                                        dl=mode, nthreads=8)
+            for a in (col, seeds, px):
+                a.setflags(write=False)
+            frames[key] = (col, seeds, px, cnt)
+        return frames[key]
+
+    return scene, ref
+
+
+class Launcher:
+    """One prepared scene and device buffers of one frame size."""
+
+    def __init__(self, rt, S, n, cam, w, h):
+        import torch
+        self.rt, self.torch, self.cam, self.w, self.h = rt, torch, cam, w, h
+        self.sc = rt.SmallptScene(S, n)
+        self.dev = torch.device("cuda", 0)
+        self.seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(self.dev)
+        self.all_groups = torch.arange(rt.lib().spt_group_count(w, h), dtype=torch.int32, device=self.dev)
+
+    def render(self, mode, counted, as_list=False, rows=None):
+        """One launch of SPP samples from the initial state: (colours, seeds,
+        pixels, counters or None).  as_list: the whole frame as a group list
+        without a cost pointer (an order, so the tiers apply)."""
+        torch, rt, w, h = self.torch, self.rt, self.w, self.h
+        col = torch.zeros(3 * w * h, dtype=torch.float32, device=self.dev)
+        seeds = torch.zeros_like(self.seeds0)
+        px = torch.zeros(w * h, dtype=torch.int32, device=self.dev)
+        cnt = torch.zeros(4, dtype=torch.int64, device=self.dev)
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        cp = cnt.data_ptr() if counted else None
+        L = rt.lib()
+        if as_list:
+            rt.check(L.spt_scene_render_list_async(self.sc.handle, C.byref(self.cam), col.data_ptr(),
+                                                   self.seeds0.data_ptr(), seeds.data_ptr(), px.data_ptr(), w, h,
+                                                   self.all_groups.data_ptr(), len(self.all_groups), 0, SPP, mode, cp,
+                                                   None, st))
+        else:
+            r0, r1 = rows or (0, h)
+            rt.check(L.spt_scene_render_async(self.sc.handle, C.byref(self.cam), col.data_ptr(),
+                                              self.seeds0.data_ptr(), seeds.data_ptr(), px.data_ptr(), w, h, r0, r1, 0,
+                                              SPP, mode, cp, st))
+        torch.cuda.synchronize()
+        return (col.cpu().numpy(), seeds.cpu().numpy().view(np.uint32), px.cpu().numpy().view(np.uint32),
+                cnt.tolist() if counted else None)
+
+    def close(self):
+        self.sc.close()
+
+
+def _same(got, ref):
+    """_check of test_gpu_smallpt.py: HDR bits, seeds, pixels, and all four
+    counters of a counted launch."""
+    gcol, gseeds, gpx, gcnt = got
+    rcol, rseeds, rpx, rcnt = ref
+    diff = gcol.view(np.uint32) != rcol.view(np.uint32)
+    assert not diff.any(), "HDR not bit-exact (%d slots, max |d| %g)" % (
+        diff.sum(), np.abs(gcol.astype(np.float64) - rcol).max())
+    assert (gseeds == rseeds).all()
+    assert (gpx == rpx).all()
+    if gcnt is not None:
+        assert gcnt == rcnt, (gcnt, rcnt)
+
+
+def _open(rt, world, name, w, h):
+    S, n, cam = world[0](name)
+    return Launcher(rt, S, n, cam(w, h), w, h)
+
+
+def _counted_and_uncounted(lz, ref, mode, expect, **kw):
+    """A counted and an uncounted launch, both equal to the oracle's frame
+    (so the uncounted launch gives the counted one's bits); after each, the
+    launch words of info() must contain `expect`."""
+    for counted in (True, False):
+        before = lz.sc.info()["launches"]
+        got = lz.render(mode, counted, **kw)
+        info = lz.sc.info()
+        assert info["launches"] == before + 1
+        for k, v in expect.items():
+            assert info[k] == v, (k, info)
+        _same(got, ref)
+
+
+# ---- layouts -------------------------------------------------------------
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name", ["leaf12", "leaf16", "nowide"])
+def test_layouts_the_library_picks(rt, world, monkeypatch, name, mode):
+    """No environment variable set: cloud(30,000) walks an 8-wide tree with
+    leaves of up to 12 spheres (three four-sphere passes per leaf), cloud(43,000)
+    one with leaves of 16, cloud(56,000) fits no 8-wide tree and walks the
+    binary one."""
+    for k in ("RT_SPT_WIDE", "RT_SPT_NO_BVH", "RT_SPT_GEO", "RT_SPT_TUNE"):
+        monkeypatch.delenv(k, raising=False)
+    w, h = FRAME
+    lz = _open(rt, world, name, w, h)
+    try:
+        info = lz.sc.info()
+        n, leaf = sl.LAYOUT_SCENES[name]
+        assert info["nspheres"] == n and info["nlights"] == 3 and info["nalways"] == 2 and not info["no_refr"]
+        assert info["launches"] == 0
+        if leaf:
+            assert info["family"] == "GEO_WIDE" and info["leaf_max"] == leaf and info["wdepth"] >= 2, info
+        else:
+            assert info["family"] == "GEO_BVH" and info["leaf_max"] == 0 and info["wnodes"] == 0, info
+        assert info["nodes"] > n // 4
+        _counted_and_uncounted(lz, world[1](name, w, h, mode), mode, {"cg": 0, "two_query": False})
+        if leaf:
+            # the last launch was uncounted: the nodes without the counted walk's 32 B of
+            # highest indices each, and one 256-B stack level per wave and level below the root
+            assert lz.sc.info()["lds_bytes"] == 112 * info["wnodes"] + 16 * 256 * (info["wdepth"] - 1)
+    finally:
+        lz.close()
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name", ["leaf12", "leaf16"])
+def test_binary_walk_on_the_large_trees(rt, world, monkeypatch, name, mode):
+    """RT_SPT_WIDE=0 on the leaf-12 and leaf-16 scenes: the binary walk over
+    trees other than configs[4]'s."""
+    monkeypatch.setenv("RT_SPT_WIDE", "0")
+    w, h = FRAME
+    lz = _open(rt, world, name, w, h)
+    try:
+        info = lz.sc.info()
+        assert info["family"] == "GEO_BVH" and info["leaf_max"] == 0 and info["nalways"] == 2, info
+        _counted_and_uncounted(lz, world[1](name, w, h, mode), mode, {"cg": 0})
+    finally:
+        lz.close()
+
+
+# ---- cooperative tiers -----------------------------------------------------
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("G", [8, 4, 2])
+@pytest.mark.parametrize("name", ["leaf8", "leaf12", "leaf16"])
+def test_cooperative_tiers_forced_in_one_launch(rt, world, monkeypatch, name, G, mode):
+    """wide_walk_coop<G> on scenes with SPEC and REFR spheres and three
+    lights, in both estimators: the whole frame as a list (an order, so the
+    tiers apply at the first launch) with every tile cooperative."""
+    w, h = FRAME
+    ntiles = ((w + 7) // 8) * ((h + 7) // 8)
+    monkeypatch.setenv("RT_SPT_TUNE", "coop=%d,coop_g=%d" % (ntiles, G))
+    lz = _open(rt, world, name, w, h)
+    try:
+        info = lz.sc.info()
+        assert info["family"] == "GEO_WIDE" and info["leaf_max"] == sl.LAYOUT_SCENES[name][1], info
+        _counted_and_uncounted(lz, world[1](name, w, h, mode), mode, {"cg": G, "n1": ntiles, "n2": 0},
+                               as_list=True)
+    finally:
+        lz.close()
+
+
+def test_cooperative_tier_of_a_learnt_order(rt, world, monkeypatch):
+    """The same key launched three times through spt_scene_render_async: the
+    first launch records the tile costs, and by the third the learnt order is
+    in use with the window class's default tier -- at this size eight lanes
+    per pixel.  Direct lighting on cloud(3000); uncounted launches and
+    counted ones (which learn an order of their own); every frame equals the
+    oracle's."""
+    monkeypatch.delenv("RT_SPT_TUNE", raising=False)
+    monkeypatch.delenv("RT_SPT_SCHED", raising=False)
+    w, h = FRAME
+    lz = _open(rt, world, "leaf8", w, h)
+    try:
+        ref = world[1]("leaf8", w, h, 1)
+        for counted in (False, True):
+            for i in range(3):
+                _same(lz.render(1, counted), ref)
+                info = lz.sc.info()
+                if i == 0:
+                    assert info["cg"] == 0 and info["n1"] == 0, info       # no order yet: a lane per pixel
+            assert info["family"] == "GEO_WIDE" and info["cg"] == 8 and info["n1"] > 0, info
+    finally:
+        lz.close()
+
+
+# ---- edges of the partition -------------------------------------------------
+WALKS = [pytest.param("wide", id="wide"), pytest.param("binary", id="binary"), pytest.param("coop8", id="coop8")]
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("walk", WALKS)
+@pytest.mark.parametrize("name", list(sl.EDGE_SCENES))
+def test_partition_edges(rt, world, monkeypatch, name, walk, mode):
+    """No always sphere; more candidates than MAX_ALWAYS (four huge spheres
+    in the tree); the smallest tree; spheres sharing a centre and exact
+    duplicates (the tie rule shows in the colour and in the counters)."""
+    w, h = FRAME
+    ntiles = ((w + 7) // 8) * ((h + 7) // 8)
+    monkeypatch.delenv("RT_SPT_TUNE", raising=False)
+    if walk == "binary":
+        monkeypatch.setenv("RT_SPT_WIDE", "0")
+    if walk == "coop8":
+        monkeypatch.setenv("RT_SPT_TUNE", "coop=%d,coop_g=8" % ntiles)
+    lz = _open(rt, world, name, w, h)
+    try:
+        info = lz.sc.info()
+        assert info["family"] == ("GEO_BVH" if walk == "binary" else "GEO_WIDE"), info
+        assert info["leaf_max"] == (0 if walk == "binary" else 8)
+        assert info["nalways"] == {"no_always": 0, "many_always": 16, "n256": 1, "coincident": 1}[name], info
+        expect = {"cg": 8, "n1": ntiles} if walk == "coop8" else {"cg": 0}
+        _counted_and_uncounted(lz, world[1](name, w, h, mode), mode, expect, as_list=walk == "coop8")
+    finally:
+        lz.close()
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_one_sphere_below_the_threshold(rt, world, mode):
+    """n256 without its last sphere gets no hierarchy: the LDS full scan."""
+    w, h = FRAME
+    lz = _open(rt, world, "n255", w, h)
+    try:
+        info = lz.sc.info()
+        assert info["family"] == "GEO_LDS" and info["nspheres"] == 255 and info["nodes"] == 0, info
+        _counted_and_uncounted(lz, world[1]("n255", w, h, mode), mode, {"cg": 0, "two_query": False})
+    finally:
+        lz.close()
+
+
+# ---- tiny frames -------------------------------------------------------------
+TINY = [(1, 1), (9, 3), (7, 70)]
+TARGETS = [pytest.param("leaf8", {}, "GEO_WIDE", id="cloud-wide"),
+           pytest.param("leaf8", {"RT_SPT_WIDE": "0"}, "GEO_BVH", id="cloud-binary"),
+           pytest.param("cornell", {"RT_SPT_TUNE": "wpb=4"}, "GEO_LDS", id="cornell-wpb4"),
+           pytest.param("cornell", {"RT_SPT_TUNE": "wpb=16"}, "GEO_LDS", id="cornell-wpb16")]
+
+
+def _tiny_open(rt, world, monkeypatch, name, env, family, w, h):
+    monkeypatch.delenv("RT_SPT_TUNE", raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    lz = _open(rt, world, name, w, h)
+    assert lz.sc.info()["family"] == family
+    return lz
+
+
+@pytest.mark.parametrize("name,env,family", TARGETS)
+@pytest.mark.parametrize("w,h", TINY)
+def test_tiny_frames(rt, world, monkeypatch, w, h, name, env, family):
+    """Frames of one pixel, of one ragged tile row and of one ragged tile
+    column: the persistent grid is one block of mostly idle waves."""
+    lz = _tiny_open(rt, world, monkeypatch, name, env, family, w, h)
+    try:
+        ntiles = ((w + 7) // 8) * ((h + 7) // 8)
+        expect = {"cg": 0, "two_query": name == "cornell"}
+        if family == "GEO_WIDE":
+            expect.update(wpb=16, nblocks=1)                   # fewer tiles than one block's waves
+        elif family == "GEO_LDS":
+            wpb = int(env["RT_SPT_TUNE"][4:])
+            expect.update(wpb=wpb, nblocks=(ntiles + wpb - 1) // wpb)
+        for mode in (0, 1):
+            if mode == 1:
+                expect["two_query"] = False
+            _counted_and_uncounted(lz, world[1](name, w, h, mode), mode, expect)
+    finally:
+        lz.close()
+
+
+@pytest.mark.parametrize("name,env,family", TARGETS)
+def test_tiny_frame_row_window(rt, world, monkeypatch, name, env, family):
+    """9x3, rows [1, 2): the window's row equals the oracle's and every
+    colour, pixel and seed slot outside it keeps its sentinel."""
+    import torch
+    w, h, r0, r1 = 9, 3, 1, 2
+    lz = _tiny_open(rt, world, monkeypatch, name, env, family, w, h)
+    try:
+        S, n, cam = world[0](name)
+        for mode in (0, 1):
+            full = world[1](name, w, h, mode)                      # pixels are independent: the window's slots
+            ref = world[1](name, w, h, mode, (r0, r1))             # ... and the oracle's own window render agree
+            inside = np.zeros((h, w), bool)
+            inside[h - r1:h - r0] = True                           # accumulator and seed rows are flipped
+            ins = inside.reshape(-1)
+            assert (ref[0].view(np.uint32).reshape(-1, 3)[ins] == full[0].view(np.uint32).reshape(-1, 3)[ins]).all()
+            col = torch.full((3 * w * h,), -7.25, dtype=torch.float32, device=lz.dev)
+            px = torch.full((w * h,), 0x25A5A5A5, dtype=torch.int32, device=lz.dev)
+            sout = torch.full((2 * w * h,), 0x5EADBEEF, dtype=torch.int32, device=lz.dev)
+            cnt = torch.zeros(4, dtype=torch.int64, device=lz.dev)
+            st = torch.cuda.current_stream(lz.dev).cuda_stream
+            rt.check(rt.lib().spt_scene_render_async(lz.sc.handle, C.byref(lz.cam), col.data_ptr(),
+                                                     lz.seeds0.data_ptr(), sout.data_ptr(), px.data_ptr(), w, h, r0,
+                                                     r1, 0, SPP, mode, cnt.data_ptr(), st))
+            torch.cuda.synchronize()
+            gcol = col.cpu().numpy().reshape(-1, 3)
+            gpx = px.cpu().numpy().view(np.uint32).reshape(h, w)
+            gs = sout.cpu().numpy().view(np.uint32).reshape(-1, 2)
+            assert (gcol[ins].view(np.uint32) == ref[0].reshape(-1, 3)[ins].view(np.uint32)).all()
+            assert (gcol[~ins] == np.float32(-7.25)).all()
+            assert (gpx[r0:r1] == ref[2].reshape(h, w)[r0:r1]).all()
+            assert (np.delete(gpx, np.s_[r0:r1], 0) == 0x25A5A5A5).all()
+            assert (gs[ins] == ref[1].reshape(-1, 2)[ins]).all() and (gs[~ins] == 0x5EADBEEF).all()
+            assert cnt.tolist() == ref[3], (cnt.tolist(), ref[3])
+    finally:
+        lz.close()
