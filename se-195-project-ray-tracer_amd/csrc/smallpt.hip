@@ -227,6 +227,35 @@ __device__ __forceinline__ void query2_bf(const G &geo, const ray3 &r, float &t,
     }
 }
 
+// One shadow ray's any-hit query (IntersectP, geomfunc.h:94-110) for lanes
+// with `have` set: query2_bf's uncounted shadow half on its own -- the same
+// test, an occluded flag, and the wave's redo with the exact query when a lane
+// that holds a ray meets |det| < 2^-96.  (Lanes without a ray run the loop on
+// whatever their registers hold; their result is discarded.)
+template <class G>
+__device__ __forceinline__ bool shadow_bf(const G &geo, const ray3 &rs, float maxt, bool have)
+{
+    bool bad = false, occ = false;
+#pragma unroll RT_SPT_QUNROLL
+    for (int i = geo.count() - 1; i >= 0; i--) {
+        const float4 g = geo.at(i);
+        const float opx = g.x - rs.o.x, opy = g.y - rs.o.y, opz = g.z - rs.o.z;
+        const float b = opx * rs.d.x + opy * rs.d.y + opz * rs.d.z;
+        const float det = b * b - (opx * opx + opy * opy + opz * opz) + g.w;
+        bad = bad || (have && fabsf(det) < 0x1p-96f);
+        const float sd = sqrt_nr(det);
+        const float t1 = b - sd, t2 = b + sd;
+        const float d = t1 > EPS ? t1 : t2;
+        occ = occ || (d > EPS && d < maxt);
+    }
+    if (wave_any(bad)) {
+        float ts = maxt;
+        int first = -1;
+        occ = query<false>(geo, rs, ts, first) >= 0;
+    }
+    return occ;
+}
+
 // ---------------------------------------------------------------------------
 // The sphere hierarchy's device code for large scenes -- BvhView, the binary
 // walk, the 8-wide walk in LDS and its cooperative form -- stands here, inside
@@ -244,7 +273,7 @@ struct Counts { unsigned isect, isectp, samples; unsigned long long tests; };
 // product build.
 #ifdef RT_SPT_PROF
 enum { PB_ITER, PB_SHADOW, PB_NEAREST, PB_DIFF, PB_SPEC, PB_REFR, PB_LIGHT, PB_BOUNCE, PB_DONE,
-       PB_WCALL, PB_WSTEP, PB_WLEAF, PB_WSHADE, PB_N };
+       PB_WCALL, PB_WSTEP, PB_WLEAF, PB_WSHADE, PB_FLUSH, PB_N };
 __device__ unsigned long long g_spt_prof[2 * PB_N];
 #define SPT_PROF(b)                                                                        \
     do {                                                                                   \
@@ -286,7 +315,9 @@ __device__ __forceinline__ int to_int(float x)
 //     VGPRs, private segment 0) and not kept: 8 waves cap the kernel at 80
 //     SGPRs, the rest go through v_readlane in every iteration (+1.05 % VALU
 //     instructions), and the eighth wave buys no rate: 16.98 ms against
-//     16.57 ms for the same code at 7 (profiles/r07);
+//     16.57 ms for the same code at 7 (profiles/r07).  With
+//     its shadow rays deferred to the per-wave ring (DQ) it holds 70 VGPRs
+//     (71 reading the spheres from global memory);
 //   binary-hierarchy (GEO_BVH) kernels: 6 -- 93 -> 80 VGPRs (2 spilled): the
 //     latency-bound walk gains more from the sixth wave than the spills cost;
 //   8-wide (GEO_WIDE) kernels: 4 -- 126 VGPRs unbounded; 5 or 6 spill;
@@ -297,6 +328,12 @@ constexpr int GS_BYTES = 6160;      // GEO_BVH group staging strip: 8 x 96 colou
 constexpr int PARK_SLOTS = 3;       // full-scan kernels' parked per-lane state: the running-average colour
 constexpr int PARK_BYTES_PER_WAVE = PARK_SLOTS * 64 * 4;
 constexpr int PARK_HEAD_BYTES = 64;  //   and, before the waves' areas, the block's copy of the camera terms
+// The uncounted two-query kernel (DQ below): per wave nine lane-private slots --
+// the colour, the parked previous sample's radiance, the second pending
+// contribution -- then the shadow-ray ring, seven dwords per entry as SoA.
+constexpr int DQ_SLOTS = 9;
+constexpr int DQ_DW_PER_WAVE = DQ_SLOTS * 64 + 7 * sptpolicy::SQ_RING;
+constexpr int DQ_BYTES_PER_WAVE = 4 * DQ_DW_PER_WAVE;
 
 // DUAL (path tracing, full-scan geometry, scenes with exactly one light): a
 // DIFF vertex builds its light sample's shadow ray AND its bounce ray in the
@@ -305,6 +342,9 @@ constexpr int PARK_HEAD_BYTES = 64;  //   and, before the waves' areas, the bloc
 // the next iteration queries both (query2_bf) and applies the shadow result
 // (rad += thr * Ld, geomfunc.h:229-230) before it shades the bounce's hit.
 // One iteration per path vertex instead of two for a lit DIFF vertex.
+// The uncounted form (no COUNT, no RAYS) goes further: the shadow ray is not
+// traced by the lane that built it nor in the next iteration, but from a
+// per-wave ring by whichever lane pops it (DQ, in the kernel).
 // COUNT: all four counters (the sphere-test count needs IntersectP's early-
 // exit position, so a counted shadow query finds the highest-index
 // occluder).  RAYS (SPT_COUNT_RAYS): Intersect / IntersectP calls and samples
@@ -340,9 +380,36 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
     // writes its dwords, so no barrier is needed); the camera terms sit
     // once per block before it.  Arithmetic, draws and stores are unchanged.
     constexpr bool PARK = GEO == GEO_LDS || GEO == GEO_GLOBAL;
+    // DQ (the uncounted two-query kernels): the shadow rays are deferred.  A
+    // lit DIFF vertex pushes its shadow ray (origin, direction, maxt) into a
+    // wave-private FIFO ring in LDS and keeps the contribution c = thr * (e *
+    // s) it would add -- the same two products on the same thr that the lock-
+    // step form computes one iteration later -- and the path query is the one-
+    // ray query_bf.  A flush pass (all 64 lanes pop the oldest min(count, 64)
+    // entries, one each, and run the any-hit loop; the result is one ballot,
+    // an owner reads the bit at its entry's distance from the head) runs when
+    // the ring holds the threshold T (spt_policy.h, sq=T) or an order demands
+    // it.  Exactness is the order of the float additions: a sample's rad
+    // receives its terms in vertex order, and the running average receives
+    // samples in sample order.  A lane's entries resolve in push order (FIFO),
+    // so its shadow terms stay ordered among themselves; a flush is forced
+    // (wave_any, before the dependent operation) when a lane
+    //   * is about to add an emitter term to a sample with a pending term,
+    //   * is about to end a sample while its previous sample is unfolded (a
+    //     sample that ends with terms pending parks its rad in LDS and is
+    //     folded into the average when the last of them resolves),
+    //   * is about to push with both its pending slots taken (one in
+    //     registers, one in LDS), or
+    //   * when no lane has a sample left: the drain that ends the wave's loop.
+    // Every lane of the wave stays in the loop until then (a lane out of
+    // samples, or past the frame's edge, idles but still pops entries).
+    constexpr bool DQ = DUAL && !COUNT && !RAYS && PARK;
+    constexpr int WAVE_DW = DQ ? DQ_DW_PER_WAVE : PARK_SLOTS * 64;
+    constexpr int SQ_RING = sptpolicy::SQ_RING;
     // Dynamic LDS carve (16-B multiples): geo | emi | col (n each) | lrec (3 per light),
     // a copy of the scene's global SoA (spt_scene_create); PARK: then the
-    // parking area, PARK_HEAD_BYTES and PARK_BYTES_PER_WAVE per wave of the block.
+    // parking area, PARK_HEAD_BYTES and PARK_BYTES_PER_WAVE (DQ:
+    // DQ_BYTES_PER_WAVE) per wave of the block.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int park_off = (PARK && LDS) ? 16 * (3 * nspheres + 3 * (nlights > 0 ? nlights : 1)) : 0;
     // (the thread index is re-read behind an empty asm at every use: hoisted
@@ -350,7 +417,13 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
     const auto park_ptr = [&]() {
         int t = (int)threadIdx.x;
         asm volatile("" : "+v"(t));
-        return (float *)(smem + park_off + PARK_HEAD_BYTES) + (t >> 6) * (PARK_SLOTS * 64) + (t & 63);
+        return (float *)(smem + park_off + PARK_HEAD_BYTES) + (t >> 6) * WAVE_DW + (t & 63);
+    };
+    // DQ: the wave's ring, field f of entry e at [f * SQ_RING + e]
+    const auto ring_ptr = [&]() {
+        int t = (int)threadIdx.x;
+        asm volatile("" : "+v"(t));
+        return (float *)(smem + park_off + PARK_HEAD_BYTES) + (t >> 6) * WAVE_DW + DQ_SLOTS * 64;
     };
     // The camera terms of pass B (twelve floats, with 1 / w and 1 / h) head
     // the parking area: read there by every lane at one address (broadcast)
@@ -514,7 +587,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
               const unsigned long long tr_c0 = __builtin_amdgcn_s_memtime();
               const unsigned long long tr_t0 = __builtin_amdgcn_s_memrealtime();
               unsigned tr_iters = 0;)
-    if (active || refill) {
+    if (active || refill || DQ) {       // (DQ: lanes without a pixel idle in the loop and pop ring entries)
         int i = (h - y - 1) * w + x;                            // smallptCPU.cpp:86
         uint32_t s0 = 0, s1 = 0;
         v3 col = mk(0.f, 0.f, 0.f);
@@ -578,6 +651,31 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
         SPT_TRACE(walk.tr_leaf = walk.tr_trips = walk.tr_leafruns = 0;)
         SPT_PROF_ONLY(for (int b = 0; b < 3; b++) walk.pf_l[b] = walk.pf_w[b] = 0;)
         bool walking = false;  //   and whether it is suspended mid-walk
+        // DQ: the lane's pending contributions, oldest first (npend of them:
+        // pc0 in registers, the second in LDS slots 6..8; their ring positions
+        // in pidx's bytes 0 and 1), of which the oldest npark belong to the
+        // parked previous sample (LDS slots 3..5); and the wave's ring, q_count
+        // entries from q_head (wave-uniform), flushed at q_T.
+        v3 pc0 = mk(0.f, 0.f, 0.f);
+        int pidx = 0, npend = 0, npark = 0;
+        int q_head = 0, q_count = 0;
+        const int q_T = sptpolicy::sq_threshold(sptpolicy::sflags_sq(sflags));
+        // DQ: sample number `current`'s radiance r into the parked running
+        // average (:110-118, the arithmetic of the PARK form below)
+        const auto fold = [&](const v3 r, const int current) {
+            float *p = park_ptr();
+            v3 c = r;
+            if (current != 0) {
+                const float k1 = (float)current;
+                const float k2 = rcp_nr(k1 + 1.f);
+                c.x = (p[0] * k1 + r.x) * k2;
+                c.y = (p[64] * k1 + r.y) * k2;
+                c.z = (p[128] * k1 + r.z) * k2;
+            }
+            p[0] = c.x;
+            p[64] = c.y;
+            p[128] = c.z;
+        };
         constexpr float nc = 1.f, nt = 1.5f;
         // prio_sched: the three level boundaries as fractions of the samples
         // (8 bits each, in 1/256; host: prio_schedule).  Every wave starts at
@@ -700,7 +798,14 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                 }
                 need_bounce = need_cam = false;
             }
-            if (k >= nsamples) {
+            // DQ: a lane out of samples stays (live = false) until the wave
+            // has none left and the ring is empty.
+            const bool live = !DQ || k < nsamples;
+            bool drain = false;
+            if constexpr (DQ) {
+                drain = !wave_any(live);
+                if (drain && q_count == 0) break;
+            } else if (k >= nsamples) {
                 if (!refill || exhausted) break;
                 continue;                       // (a pixel past the frame's edge: claim again)
             }
@@ -725,7 +830,69 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
             int first = -1;
             int id;
             bool done = false, lights = false, a_R = false;
-            if constexpr (DUAL) {
+            bool pushed = false;            // DQ: the lane pushed a shadow ray in this iteration
+            if constexpr (DQ) {
+                id = -1;
+                if (live) id = query_bf<COUNT>(geo, ray, t, first);
+                // What this lane's shading is about to do that an unresolved
+                // entry must precede: add an emitter term, end its sample, push.
+                bool f_emit = false, f_ends = false, f_diff = false;
+                if (live && npend > 0) {
+                    bool emit = false;
+                    if (id >= 0) {
+                        const float4 oe = S.emi[id];
+                        emit = !((oe.x == 0.f) && (oe.x == 0.f) && (oe.z == 0.f));
+                        f_diff = !emit && __float_as_int(oe.w) == DIFF;
+                    }
+                    f_emit = emit && specular;
+                    f_ends = id < 0 || emit || depth >= 6;
+                }
+                while (true) {
+                    const bool force = (f_emit && npend > npark) || (f_ends && npark > 0) || (f_diff && npend == 2);
+                    // (a forcing lane has an entry in the ring, so q_count > 0 then)
+                    if (q_count == 0 || !(sptpolicy::sq_flush(q_count, q_T) || drain || wave_any(force))) break;
+                    // ---- flush pass: lane j takes entry head + j
+                    const int m = sptpolicy::sq_pop(q_count);
+                    const int e = sptpolicy::sq_wrap(q_head + lane);
+                    const float *rg = ring_ptr();
+                    ray3 rs;
+                    rs.o = mk(rg[e], rg[SQ_RING + e], rg[2 * SQ_RING + e]);
+                    rs.d = mk(rg[3 * SQ_RING + e], rg[4 * SQ_RING + e], rg[5 * SQ_RING + e]);
+                    const float maxt = rg[6 * SQ_RING + e];
+                    const bool have = lane < m;
+                    SPT_PROF_ONLY(if (have) prof_l[PB_FLUSH]++; if (lane == 0) prof_w[PB_FLUSH]++;)
+                    const bool occ = shadow_bf(geo, rs, maxt, have);
+                    const unsigned long long unocc = __builtin_amdgcn_ballot_w64(have && !occ);
+                    // owners, oldest entry first (:154-161, then :229-230).  (The
+                    // fold stands inside the loop: hoisted behind it, to run once a
+                    // pass, it cost 13 more scalar spills and 2.3 % of the frame.)
+                    while (npend > 0) {
+                        const int rel = sptpolicy::sq_rel(pidx & 255, q_head);
+                        if (rel >= m) break;
+                        const bool lit = (unocc >> rel) & 1ull;
+                        if (npark > 0) {
+                            float *p = park_ptr();
+                            if (lit) {
+                                p[192] = p[192] + pc0.x;
+                                p[256] = p[256] + pc0.y;
+                                p[320] = p[320] + pc0.z;
+                            }
+                            npark--;
+                            if (npark == 0) fold(mk(p[192], p[256], p[320]), first_sample + k - 1);
+                        } else if (lit) {
+                            rad = vadd(rad, pc0);
+                        }
+                        npend--;
+                        pidx >>= 8;
+                        if (npend > 0) {
+                            const float *p = park_ptr();
+                            pc0 = mk(p[384], p[448], p[512]);
+                        }
+                    }
+                    q_head = __builtin_amdgcn_readfirstlane(sptpolicy::sq_wrap(q_head + m));
+                    q_count = __builtin_amdgcn_readfirstlane(q_count - m);
+                }
+            } else if constexpr (DUAL) {
                 // Both rays at once when any lane holds a shadow ray; its
                 // result is applied first (the light sample precedes the
                 // bounce's hit in the reference's order).
@@ -781,7 +948,9 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                 id = query_bf<COUNT>(geo, ray, t, first);
             }
             float dp = 0.f, inv_sign = 1.f;  // REFR (pass A): vdot(normal, ray.d), -1 * sign(dp); and id
-            if (DUAL && fin) {
+            if (DQ && !live) {
+                // no sample left: the lane only takes part in the flush passes
+            } else if (DUAL && fin) {
                 // the path ended at the last DIFF vertex: no path ray this iteration
             } else if (shadow && !DUAL) {                       // :154-161
                 SPT_PROF(PB_SHADOW);
@@ -919,8 +1088,40 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                     const float num = l_lane ? (4.f * PI_F * lc.w * lc.w) * wi * wo : (refl_pick ? Re : Tr);
                     const float den = l_lane ? len * len : (refl_pick ? P : 1.f - P);
                     const float quo = num / den;
+                    // DQ: the pushing lanes' ranks (lit is false for an R lane)
+                    unsigned long long pm = 0;
+                    if constexpr (DQ) pm = __builtin_amdgcn_ballot_w64(lit);
                     if (!with_r || a_L) {
-                        if (lit) {
+                        if (DQ && lit) {
+                            // the shadow ray into the ring, its term c = thr * (e * s) kept
+                            const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(pm >> 32),
+                                                                       __builtin_amdgcn_mbcnt_lo((unsigned)pm, 0u));
+                            const int pos = sptpolicy::sq_push_pos(q_head, q_count, rank);
+                            float *rg = ring_ptr();
+                            rg[pos] = hit.x;
+                            rg[SQ_RING + pos] = hit.y;
+                            rg[2 * SQ_RING + pos] = hit.z;
+                            rg[3 * SQ_RING + pos] = vn.x;
+                            rg[4 * SQ_RING + pos] = vn.y;
+                            rg[5 * SQ_RING + pos] = vn.z;
+                            rg[6 * SQ_RING + pos] = len - EPS;
+                            const float4 le = S.lrec[2];
+                            const v3 c = vmul(thr, vsmul(quo, mk(le.x, le.y, le.z)));   // 0 + e * s, then thr * Ld
+                            if (npend == 0) {
+                                pc0 = c;
+                                pidx = pos;
+                            } else {
+                                float *p = park_ptr();
+                                p[384] = c.x;
+                                p[448] = c.y;
+                                p[512] = c.z;
+                                pidx |= pos << 8;
+                            }
+                            npend++;
+                            pushed = true;
+                            a_L = false;
+                            lights_done = true;                 // the only light
+                        } else if (lit) {
                             if (DUAL) {
                                 sdir = vn;                      // queried next iteration, with the bounce ray
                             } else {
@@ -971,8 +1172,11 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                     if (a_L) pass_a(false);
                 }
             }
+            if constexpr (DQ)      // this iteration's pushes (one pass A: every lane is back here)
+                q_count = __builtin_amdgcn_readfirstlane(
+                    q_count + __builtin_popcountll(__builtin_amdgcn_ballot_w64(pushed)));
             if (was_R) done = depth > 6;
-            if (lights_done) {                                  // :229-230, then the bounce
+            if (lights_done) {                                 // :229-230, then the bounce
                 // (DUAL: Ld is 0 + e * s once the pending shadow ray is
                 // resolved, or 0 -- and rad + thr * 0 == rad -- if none.)
                 if (!DUAL) rad = vadd(rad, vmul(thr, lsum));
@@ -990,7 +1194,19 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
             if (done) {                                         // :110-118 running average
                 SPT_PROF(PB_DONE);
                 const int current = first_sample + k;
-                if constexpr (PARK) {
+                if constexpr (DQ) {
+                    // terms still pending: rad waits in LDS for the last of
+                    // them (the previous sample is folded by now: f_ends)
+                    if (npend > 0) {
+                        float *p = park_ptr();
+                        p[192] = rad.x;
+                        p[256] = rad.y;
+                        p[320] = rad.z;
+                        npark = npend;
+                    } else {
+                        fold(rad, current);
+                    }
+                } else if constexpr (PARK) {
                     // the same average on the parked colour: loaded, updated and written back here
                     float *p = park_ptr();
                     v3 c = rad;
@@ -1040,7 +1256,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
             }
             gs_seed[r * 64 + 2 * c] = s0;
             gs_seed[r * 64 + 2 * c + 1] = s1;
-        } else if (lead && !refill) {            // (refill: stored as each pixel finished)
+        } else if (lead && !refill && (!DQ || active)) {   // (refill: stored as each pixel finished)
             if (PARK && nsamples > 0) {          // the parked colour back
                 const float *p = park_ptr();
                 col = mk(p[0], p[64], p[128]);
@@ -1374,7 +1590,11 @@ int launch(const spt_scene &sc, const RenderCall &c, const Shape &g)
     if (geo == GEO_BVH) lds = (size_t)(g.wpb / 4) * GS_BYTES;
     // full-scan kernels: the parked per-lane state, after the scene copy (the
     // 16-wave shape's reservation below covers it unless the scene is large)
-    if (geo == GEO_LDS || geo == GEO_GLOBAL) lds += PARK_HEAD_BYTES + (size_t)g.wpb * PARK_BYTES_PER_WAVE;
+    // (the uncounted two-query kernel: with its pending slots and shadow-ray ring)
+    const bool dual = two_query_form(geo, dl, sc.nlights == 1);
+    const bool dq = dual && cmode == CNT_NONE;
+    if (geo == GEO_LDS || geo == GEO_GLOBAL)
+        lds += PARK_HEAD_BYTES + (size_t)g.wpb * (dq ? DQ_BYTES_PER_WAVE : PARK_BYTES_PER_WAVE);
     if (g.wpb == 16 && lds < 81 * 1024) lds = 81 * 1024;   // > half the CU's 160 KiB: one block per CU
     int *work = nullptr;
     if (geo == GEO_WIDE) {
@@ -1383,14 +1603,14 @@ int launch(const spt_scene &sc, const RenderCall &c, const Shape &g)
             return rtrt::check_launch("spt work counters") ? RT_ERR_HIP : RT_ERR_INVALID;
     }
     const sptpolicy::Tiers t = sptpolicy::heavy_tiers(g, sc.cus);
-    const bool dual = two_query_form(geo, dl, sc.nlights == 1);
     const Kernel kern = pick_kernel(geo, dl, cmode, dual, t.cg);
     sc.last = {sc.last.count + 1, g.wpb, g.nblocks, t.cg, t.n1, t.n2, dual ? 1 : 0, (int)lds};
     hipLaunchKernelGGL(kern, dim3(g.nblocks), dim3(64 * g.wpb), lds, c.stream, sc.d_spheres, n, *c.cam, c.colors,
                        c.seeds_in, c.seeds_out, c.pixels, c.w, c.h, c.r0, c.r1, g.tiles_x, g.ntiles, g.nslots,
                        g.gstride, c.first_sample, c.nsamples, sptpolicy::prio_schedule(g), g.order, g.cost, gg, ge, gc,
                        gl, sc.nlights, sc.bvh, c.counters, work, geo == GEO_WIDE ? sptpolicy::split_word(g, t) : 0,
-                       sptpolicy::pack_nheavy(t.n1, t.n2), sptpolicy::pack_sflags(sc.no_refr, g.cost_max));
+                       sptpolicy::pack_nheavy(t.n1, t.n2),
+                       sptpolicy::pack_sflags(sc.no_refr, g.cost_max, dq ? sptpolicy::sq_threshold(g.tune.sq) : 0));
     return RT_OK;
 }
 

@@ -48,10 +48,35 @@ SPT_HD constexpr int nheavy_n1(int nheavy) { return nheavy & 0xffff; }
 SPT_HD constexpr int nheavy_n2(int nheavy) { return (nheavy >> 16) & 0xffff; }
 
 // sflags: bit 0 = no sphere of the scene refracts, bit 2 = group costs are
-// the group's longest tile (atomic max), not the sum.
-inline int pack_sflags(bool no_refr, bool cost_max) { return (no_refr ? 1 : 0) | (cost_max ? 4 : 0); }
+// the group's longest tile (atomic max), not the sum, bits 8..14 = the flush
+// threshold of the shadow-ray ring (the uncounted two-query kernel; else 0).
+inline int pack_sflags(bool no_refr, bool cost_max, int sq = 0)
+{
+    return (no_refr ? 1 : 0) | (cost_max ? 4 : 0) | ((sq & 127) << 8);
+}
 SPT_HD constexpr bool sflags_no_refr(int sflags) { return sflags & 1; }
 SPT_HD constexpr bool sflags_cost_max(int sflags) { return sflags & 4; }
+SPT_HD constexpr int sflags_sq(int sflags) { return (sflags >> 8) & 127; }
+
+// ---- the shadow-ray ring of the uncounted two-query kernel (render_kernel,
+// DQ): per wave SQ_RING entries in LDS, a FIFO of `count` entries from `head`.
+// A flush pass runs while count >= T and pops min(count, 64) entries, one per
+// lane; a push follows only when count < T and adds at most one entry per
+// lane, so the ring never holds more than T + 63 entries and T may be at most
+// SQ_RING - 63.  Positions are in [0, SQ_RING); one conditional subtraction
+// wraps a sum of two of them, or of a position and a count.
+constexpr int SQ_RING = 112;
+constexpr int SQ_DEFAULT = 49;
+SPT_HD constexpr int sq_capacity(int T) { return T + 63; }
+SPT_HD constexpr int sq_max_threshold() { return SQ_RING - 63; }
+SPT_HD constexpr int sq_threshold(int T) { return T < 1 ? SQ_DEFAULT : (T > sq_max_threshold() ? sq_max_threshold() : T); }
+SPT_HD constexpr int sq_wrap(int i) { return i >= SQ_RING ? i - SQ_RING : i; }
+SPT_HD constexpr bool sq_flush(int count, int T) { return count >= T; }
+SPT_HD constexpr int sq_pop(int count) { return count < 64 ? count : 64; }
+// the ring position of the rank-th pushing lane's entry
+SPT_HD constexpr int sq_push_pos(int head, int count, int rank) { return sq_wrap(sq_wrap(head + count) + rank); }
+// an entry's distance from the head: it is among the m popped ones iff < m
+SPT_HD constexpr int sq_rel(int pos, int head) { return pos - head < 0 ? pos - head + SQ_RING : pos - head; }
 
 // prio_sched: the three priority-level boundaries, 8 bits each, in 1/256 of
 // the samples.
@@ -79,11 +104,14 @@ SPT_HD constexpr int prio_bound(int prio_sched, int level) { return (prio_sched 
 //               (64/128/192 for the 4-wave block shape, 128/192/224 for 16)
 //   wpb=4|16    full-scan block shape (default: by waves of work per SIMD)
 //   blocks=N    8-wide persistent grid size (default: one block per CU)
+//   sq=T        flush threshold of the shadow-ray ring, 1..64, clamped to the
+//               ring's largest (default SQ_DEFAULT; 1: a pass every iteration)
 struct SptTune {
     int coop = -1, coop_g = 0, coop_waves = -1, routed = -1;
     int budget = 16, batch = 16, stop = -1;     // (stop -1: by window, see heavy_tiers)
     int prio[3] = {-1, -1, -1};
     int wpb = 0, blocks = 0;
+    int sq = 0;                                 // (0: SQ_DEFAULT)
 };
 // The knobs of one RT_SPT_TUNE string (null: the defaults).
 inline SptTune spt_tune_parse(const char *e)
@@ -109,6 +137,7 @@ inline SptTune spt_tune_parse(const char *e)
         else if (k == "prio") sscanf(v, "%d/%d/%d", &t.prio[0], &t.prio[1], &t.prio[2]);
         else if (k == "wpb") t.wpb = atoi(v) == 16 ? 16 : 4;
         else if (k == "blocks") t.blocks = std::max(atoi(v), 0);
+        else if (k == "sq") t.sq = std::min(std::max(atoi(v), 1), 64);
     }
     return t;
 }

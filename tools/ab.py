@@ -84,7 +84,7 @@ def child():
         ts.append(a.elapsed_time(b))
     if os.environ.get("PROF"):      # block counters of a tools-only instrumented build
         names = ["iter", "shadow", "nearest", "diff", "spec", "refr", "light", "bounce", "done",
-                 "wcall", "wstep", "wleaf", "wshade"]
+                 "wcall", "wstep", "wleaf", "wshade", "flush"]   # flush: ring entries popped / passes
         buf = (C.c_ulonglong * (2 * len(names)))()
         L.spt_prof_read(buf)
         for b, nm in enumerate(names):
