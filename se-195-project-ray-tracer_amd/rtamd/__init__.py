@@ -9,7 +9,10 @@ what the tests, bench.py and __graft_entry__ drive.
     smallpt  : SmallptFrame.render(k)  ~ k x UpdateRenderingCPU
                (smallptgpu-v1.6/smallptCPU.cpp:77-132) on the GPU, or
                tiled in row bands over several GPUs (devices=[...]);
-               SmallptMulti: the device-resident multi-GPU frame (spt_multi_*)
+               SmallptMulti: the device-resident multi-GPU frame (spt_multi_*);
+               SmallptDeviceFrame (device.py): one prepared scene plus
+               device-resident buffers, launched asynchronously
+               (spt_scene_render_async / _groups_async / _list_async)
     Queue    : queue_render()  ~ raytracer_non_kernel
                (Raytracer3.2.03/.../raytracer_non_OpenCL.c:285-449) on the GPU
 """
@@ -18,12 +21,13 @@ import ctypes as C
 import numpy as np
 
 from . import ppm, scenes
+from .device import SmallptDeviceFrame
 from ._lib import (Camera, Float4, Primitive, QPrimitive, RTError, Sphere, Vec3, check, device_count, lib,
                    set_device, SPT_COST_MAX, SPT_COUNT_RAYS, SPT_LIST_SET, SPT_DIRECT_LIGHTING, SPT_PATH_TRACING)
 
 __all__ = ["Camera", "Primitive", "QPrimitive", "Float4", "Sphere", "Vec3", "RTError", "scenes", "lib", "check",
            "device_count", "set_device", "whitted_render", "queue_render", "SmallptFrame", "SmallptScene",
-           "SmallptMulti",
+           "SmallptMulti", "SmallptDeviceFrame",
            "SPT_PATH_TRACING", "SPT_DIRECT_LIGHTING", "SPT_COUNT_RAYS", "SPT_COST_MAX", "SPT_LIST_SET"]
 
 

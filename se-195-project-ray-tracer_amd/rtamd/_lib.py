@@ -143,6 +143,15 @@ def lib():
     return L
 
 
+def entry(name):
+    """lib().<name>; RTError where the loaded build (an older A/B library
+    under RT_HIP_LIB) does not export that entry point."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise RTError(RT_ERR_INVALID, "%s is not exported by %s (an older build?)" % (name, LIB_PATH))
+    return fn
+
+
 def check(rc):
     if rc != RT_OK:
         msg = lib().rt_last_error()

@@ -1,0 +1,125 @@
+"""SmallptDeviceFrame: one prepared smallpt scene plus device-resident frame
+buffers, launched asynchronously -- the path the GPU tests and the tools
+drive.  This module is the one place in the package that spells out the calls
+to spt_scene_render_async, spt_scene_render_groups_async and
+spt_scene_render_list_async (include/rt_hip.h).
+
+torch is imported inside the functions, so `import rtamd` works without it.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import scenes
+from ._lib import SPT_PATH_TRACING, check as _check, entry, lib
+
+
+def _i32(v):
+    """A 32-bit pattern given signed or unsigned, as the int32 torch fills with."""
+    return (int(v) + (1 << 31)) % (1 << 32) - (1 << 31)
+
+
+class SmallptDeviceFrame:
+    """colors / seeds / pixels / counters of one w x h frame on `device`, and
+    the launches of `scene` (a SmallptScene, borrowed: the caller closes it)
+    into them.  seeds0 holds the initial seeds and is never written.  Where
+    `device` is not the current HIP device the caller selects it
+    (rtamd.set_device) around scene creation and launches, as without the
+    class."""
+
+    def __init__(self, scene, camera, w, h, seed=1, device=0):
+        import torch
+        self.scene, self.camera, self.w, self.h = scene, camera, w, h
+        self.device = torch.device("cuda", device)
+        self.seeds0 = torch.from_numpy(scenes.seeds(w, h, seed).view(np.int32)).to(self.device)
+        self.seeds = torch.zeros_like(self.seeds0)
+        self.colors = torch.zeros(3 * w * h, dtype=torch.float32, device=self.device)
+        self.pixels = torch.zeros(w * h, dtype=torch.int32, device=self.device)
+        self.counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+
+    @property
+    def groups_total(self):
+        """spt_group_count(w, h): the frame's tile groups."""
+        return entry("spt_group_count")(self.w, self.h)
+
+    def render(self, nsamples, *, first_sample=0, mode=SPT_PATH_TRACING, counted=False, rows=None, share=None,
+               groups=None, ngroups=None, cost=None, seeds_in=None, stream=None, check=True):
+        """One asynchronous launch of samples [first_sample, first_sample +
+        nsamples) into the frame; returns the entry point's code (raises
+        RTError on failure unless check=False).  The window is at most one of
+        rows=(r0, r1) (spt_scene_render_async; the default, (0, h)),
+        share=(k, N) (spt_scene_render_groups_async) and groups=<int32 device
+        tensor> (spt_scene_render_list_async; ngroups overrides its length,
+        cost is its optional int32 d_group_cost).  counted: False (no counter
+        buffer), True (self.counters) or an int64 tensor of the caller's.
+        seeds_in defaults to seeds0; a progressive caller passes self.seeds.
+        stream (a torch stream or a raw handle) defaults to torch's current
+        stream on the frame's device at the time of the call.  Allocates
+        nothing on the device and never synchronises."""
+        if sum(x is not None for x in (rows, share, groups)) > 1:
+            raise ValueError("render: at most one of rows=, share= and groups=")
+        if groups is None and (ngroups is not None or cost is not None):
+            raise ValueError("render: ngroups= and cost= go with groups=")
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self.device)
+        L = lib()
+        # the locals below carry the header's parameter names, in its order
+        scene = self.scene.handle
+        camera = C.byref(self.camera)
+        d_colors = self.colors.data_ptr()
+        d_seeds_in = (self.seeds0 if seeds_in is None else seeds_in).data_ptr()
+        d_seeds_out = self.seeds.data_ptr()
+        d_pixels = self.pixels.data_ptr()
+        w, h = self.w, self.h
+        d_counters = None if counted is False else (self.counters if counted is True else counted).data_ptr()
+        stream = getattr(stream, "cuda_stream", stream)
+        if share is not None:
+            group, ngroups = share
+            # (scene, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h, group, ngroups, first_sample,
+            #  nsamples, mode, d_counters, stream)
+            entry("spt_scene_render_groups_async")       # (RTError where an older build lacks it)
+            rc = L.spt_scene_render_groups_async(
+                scene, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h, group, ngroups, first_sample,
+                nsamples, mode, d_counters, stream)
+        elif groups is not None:
+            d_groups = groups.data_ptr()
+            ngroups = groups.numel() if ngroups is None else ngroups
+            d_group_cost = None if cost is None else cost.data_ptr()
+            # (scene, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h, d_groups, ngroups, first_sample,
+            #  nsamples, mode, d_counters, d_group_cost, stream)
+            entry("spt_scene_render_list_async")
+            rc = L.spt_scene_render_list_async(
+                scene, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h, d_groups, ngroups, first_sample,
+                nsamples, mode, d_counters, d_group_cost, stream)
+        else:
+            row_begin, row_end = (0, h) if rows is None else rows
+            # (scene, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h, row_begin, row_end, first_sample,
+            #  nsamples, mode, d_counters, stream)
+            rc = L.spt_scene_render_async(
+                scene, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h, row_begin, row_end, first_sample,
+                nsamples, mode, d_counters, stream)
+        return _check(rc) if check else rc
+
+    def reset(self, colors=0.0, pixels=0, seeds=0):
+        """Refills the output tensors in place (pixels and seeds take a 32-bit
+        pattern) and zeroes the counters."""
+        self.colors.fill_(colors)
+        self.pixels.fill_(_i32(pixels))
+        self.seeds.fill_(_i32(seeds))
+        self.counters.zero_()
+        return self
+
+    def host(self):
+        """Synchronises the device; (colors float32, seeds uint32, pixels
+        uint32) as numpy arrays."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        return (self.colors.cpu().numpy(), self.seeds.cpu().numpy().view(np.uint32),
+                self.pixels.cpu().numpy().view(np.uint32))
+
+    def same_bits(self, other):
+        """Colours (as bit patterns), seeds and pixels equal another frame's."""
+        import torch
+        return (torch.equal(self.colors.view(torch.int32), other.colors.view(torch.int32))
+                and torch.equal(self.seeds, other.seeds) and torch.equal(self.pixels, other.pixels))

@@ -217,6 +217,19 @@ def complex10k(total=10000):
     return arr, len(rows), cam
 
 
+def smallpt(kind, w, h):
+    """(spheres, n, camera at w x h) of "cornell" or of "complex" (complex10k,
+    BASELINE configs[4]'s scene)."""
+    if kind == "cornell":
+        arr, n = cornell()
+        return arr, n, cornell_camera(w, h)
+    if kind == "complex":
+        arr, n, cam = complex10k()
+        update_camera(cam, w, h)
+        return arr, n, cam
+    raise ValueError("smallpt scene %r: cornell or complex" % (kind,))
+
+
 def seeds(width, height, seed=1):
     """AllocateBuffers' seed fill (smallptGPU.cpp:105-110): srand(seed), then
     2*width*height glibc rand() words clamped to >= 2 (spt_seed_fill)."""

@@ -6,33 +6,17 @@ Every pixel is independent (own RNG words, own accumulator: smallptCPU.cpp:
 84-123), so any partition of the frame's tile groups rendered list by list
 must give the full-frame render's bits -- which the other GPU tests pin to
 the reference (oracle, reference-core goldens)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 
-def _scene(rt, kind, w, h):
-    if kind == "cornell":
-        S, n = rt.scenes.cornell()
-        return S, n, rt.scenes.cornell_camera(w, h)
-    S, n, cam = rt.scenes.complex10k()
-    rt.scenes.update_camera(cam, w, h)
-    return S, n, cam
-
-
-class _Frame:
-    def __init__(self, torch, dev, w, h, seeds0):
-        self.col = torch.zeros(3 * w * h, dtype=torch.float32, device=dev)
-        self.seeds = torch.zeros_like(seeds0)
-        self.px = torch.zeros(w * h, dtype=torch.int32, device=dev)
-        self.cnt = torch.zeros(4, dtype=torch.int64, device=dev)
-
-    def same(self, o, torch):
-        return (torch.equal(self.col.view(torch.int32), o.col.view(torch.int32)) and torch.equal(self.seeds, o.seeds)
-                and torch.equal(self.px, o.px))
+def _open(rt, kind, w, h):
+    """A prepared scene and a function that makes a zeroed device frame of it."""
+    S, n, cam = rt.scenes.smallpt(kind, w, h)
+    sc = rt.SmallptScene(S, n)
+    return sc, lambda: rt.SmallptDeviceFrame(sc, cam, w, h)
 
 
 @pytest.mark.parametrize("kind,w,h,spp,env", [
@@ -51,35 +35,25 @@ def test_lists_partition_the_frame(rt, monkeypatch, kind, w, h, spp, env):
     from rtamd import dist as rd
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    S, n, cam = _scene(rt, kind, w, h)
-    sc = rt.SmallptScene(S, n)
-    dev = torch.device("cuda", 0)
-    seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    L = rt.lib()
-    ng = L.spt_group_count(w, h)
+    sc, frame = _open(rt, kind, w, h)
+    ref, got = frame(), frame()
+    ng = ref.groups_total
     assert ng == rd.group_count(w, h)
-    ref = _Frame(torch, dev, w, h, seeds0)
-    rt.check(L.spt_scene_render_async(sc.handle, C.byref(cam), ref.col.data_ptr(), seeds0.data_ptr(),
-                                      ref.seeds.data_ptr(), ref.px.data_ptr(), w, h, 0, h, 0, spp, 0,
-                                      ref.cnt.data_ptr(), st))
+    ref.render(spp, counted=True)
     rng = np.random.default_rng(w + h)
     perm = rng.permutation(ng)
     cuts = sorted(rng.choice(np.arange(1, ng), 2, replace=False))
     lists = [perm[:cuts[0]], perm[cuts[0]:cuts[1]], perm[cuts[1]:]]
     for mode in (0, rt.SPT_COUNT_RAYS, rt.SPT_LIST_SET):
-        got = _Frame(torch, dev, w, h, seeds0)
-        got.cnt[2] = 12345                                 # rays-only leaves counters[2] untouched
+        got.reset()
+        got.counters[2] = 12345                            # rays-only leaves counters[2] untouched
         for i, lst in enumerate(lists):
             # out-of-range entries: skipped (SPT_LIST_SET: the caller promises none, and no dedup pass runs)
             lst = list(lst) + ([-7, ng, 1 << 30] if i == 1 and mode != rt.SPT_LIST_SET else [])
-            d = torch.tensor(lst, dtype=torch.int32, device=dev)
-            rt.check(L.spt_scene_render_list_async(sc.handle, C.byref(cam), got.col.data_ptr(), seeds0.data_ptr(),
-                                                   got.seeds.data_ptr(), got.px.data_ptr(), w, h, d.data_ptr(),
-                                                   len(lst), 0, spp, mode, got.cnt.data_ptr(), None, st))
+            got.render(spp, mode=mode, counted=True, groups=torch.tensor(lst, dtype=torch.int32, device=got.device))
         torch.cuda.synchronize()
-        assert got.same(ref, torch), mode
-        c, r = got.cnt.tolist(), ref.cnt.tolist()
+        assert got.same_bits(ref), mode
+        c, r = got.counters.tolist(), ref.counters.tolist()
         if mode == rt.SPT_COUNT_RAYS:
             assert (c[0], c[1], c[3]) == (r[0], r[1], r[3]) and c[2] == 12345, (c, r)
         else:
@@ -92,21 +66,14 @@ def test_list_costs_and_bad_arguments(rt):
     frame's group count is refused."""
     import torch
     w, h = 320, 180
-    S, n, cam = _scene(rt, "complex", w, h)
-    sc = rt.SmallptScene(S, n)
-    dev = torch.device("cuda", 0)
-    seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    L = rt.lib()
-    ng = L.spt_group_count(w, h)
-    f = _Frame(torch, dev, w, h, seeds0)
+    sc, frame = _open(rt, "complex", w, h)
+    f = frame()
+    dev, ng = f.device, f.groups_total
     lst = list(range(0, ng, 3))
     d = torch.tensor(lst, dtype=torch.int32, device=dev)
     cost = torch.zeros(ng, dtype=torch.int32, device=dev)
     for cbuf in (None, cost):                 # (a warm-up launch first: the timed ones compare)
-        rt.check(L.spt_scene_render_list_async(sc.handle, C.byref(cam), f.col.data_ptr(), seeds0.data_ptr(),
-                                               f.seeds.data_ptr(), f.px.data_ptr(), w, h, d.data_ptr(), len(lst), 0,
-                                               2, 0, None, cbuf.data_ptr() if cbuf is not None else None, st))
+        f.render(2, groups=d, cost=cbuf)
     torch.cuda.synchronize()
     c = cost.cpu().numpy()
     mask = np.zeros(ng, bool)
@@ -117,16 +84,14 @@ def test_list_costs_and_bad_arguments(rt):
     # quarter of them (two launches' wave times, so only in aggregate); the
     # same frame
     cmax = torch.zeros(ng, dtype=torch.int32, device=dev)
-    f2 = _Frame(torch, dev, w, h, seeds0)
-    rt.check(L.spt_scene_render_list_async(sc.handle, C.byref(cam), f2.col.data_ptr(), seeds0.data_ptr(),
-                                           f2.seeds.data_ptr(), f2.px.data_ptr(), w, h, d.data_ptr(), len(lst), 0, 2,
-                                           rt.SPT_COST_MAX, None, cmax.data_ptr(), st))
+    f2 = frame()
+    f2.render(2, mode=rt.SPT_COST_MAX, groups=d, cost=cmax)
     torch.cuda.synchronize()
     m = cmax.cpu().numpy().astype(np.int64)
     assert (m[mask] > 0).all() and (m[~mask] == 0).all()
     ratio = m[mask].sum() / c[mask].sum()
     assert 0.15 < ratio < 0.9, ratio
-    assert torch.equal(f2.col.view(torch.int32), f.col.view(torch.int32)) and torch.equal(f2.px, f.px)
+    assert torch.equal(f2.colors.view(torch.int32), f.colors.view(torch.int32)) and torch.equal(f2.pixels, f.pixels)
     # Full counters (the refilling kernel: a lane's unit is a pixel): the sum
     # of each group's pixel durations, or with SPT_COST_MAX the longest one --
     # which no launch can exceed (100 MHz ticks against the launch's own
@@ -135,27 +100,22 @@ def test_list_costs_and_bad_arguments(rt):
     cmx = torch.zeros(ng, dtype=torch.int32, device=dev)
     cnt = torch.zeros(4, dtype=torch.int64, device=dev)
     for mode, cb in ((0, csum), (rt.SPT_COST_MAX, cmx)):
-        f3 = _Frame(torch, dev, w, h, seeds0)
+        f3 = frame()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        rt.check(L.spt_scene_render_list_async(sc.handle, C.byref(cam), f3.col.data_ptr(), seeds0.data_ptr(),
-                                               f3.seeds.data_ptr(), f3.px.data_ptr(), w, h, d.data_ptr(), len(lst), 0,
-                                               2, mode, cnt.data_ptr(), cb.data_ptr(), st))
+        f3.render(2, mode=mode, counted=cnt, groups=d, cost=cb)
         e1.record()
         torch.cuda.synchronize()
-        assert torch.equal(f3.col.view(torch.int32), f.col.view(torch.int32)) and torch.equal(f3.px, f.px)
+        assert torch.equal(f3.colors.view(torch.int32), f.colors.view(torch.int32))
+        assert torch.equal(f3.pixels, f.pixels)
     launch_ticks = e0.elapsed_time(e1) * 1e5
     s, mx = csum.cpu().numpy().astype(np.int64), cmx.cpu().numpy().astype(np.int64)
     assert (mx[mask] > 0).all() and (mx[~mask] == 0).all() and (s[mask] > 0).all()
     assert mx.max() <= 1.05 * launch_ticks + 1000, (mx.max(), launch_ticks)
     assert mx[mask].sum() < 0.5 * s[mask].sum(), (mx[mask].sum(), s[mask].sum())
-    assert L.spt_scene_render_list_async(sc.handle, C.byref(cam), f2.col.data_ptr(), seeds0.data_ptr(),
-                                         f2.seeds.data_ptr(), f2.px.data_ptr(), w, h, d.data_ptr(), len(lst), 0, 1,
-                                         0x400, None, None, st) == rt._lib.RT_ERR_INVALID
+    assert f2.render(1, mode=0x400, groups=d, check=False) == rt._lib.RT_ERR_INVALID
     big = torch.zeros(ng + 1, dtype=torch.int32, device=dev)
-    assert L.spt_scene_render_list_async(sc.handle, C.byref(cam), f.col.data_ptr(), seeds0.data_ptr(),
-                                         f.seeds.data_ptr(), f.px.data_ptr(), w, h, big.data_ptr(), ng + 1, 0, 1, 0,
-                                         None, None, st) == rt._lib.RT_ERR_INVALID
+    assert f.render(1, groups=big, ngroups=ng + 1, check=False) == rt._lib.RT_ERR_INVALID
 
 
 @pytest.mark.parametrize("kind", ["cornell", "complex"])
@@ -168,39 +128,22 @@ def test_list_repeated_entries_render_once(rt, kind):
     whole frame as a list equals the full-frame render."""
     import torch
     w, h = 160, 96
-    S, n, cam = _scene(rt, kind, w, h)
-    sc = rt.SmallptScene(S, n)
+    sc, new_frame = _open(rt, kind, w, h)
     dev = torch.device("cuda", 0)
-    seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    L = rt.lib()
-    ng = L.spt_group_count(w, h)
+    ng = rt.lib().spt_group_count(w, h)
 
     def frame(lst, cost=None):
-        f = _Frame(torch, dev, w, h, seeds0)
-        if lst is None:
-            rt.check(L.spt_scene_render_async(sc.handle, C.byref(cam), f.col.data_ptr(), seeds0.data_ptr(),
-                                              f.seeds.data_ptr(), f.px.data_ptr(), w, h, 0, h, 0, 2, 0,
-                                              f.cnt.data_ptr(), st))
-            rt.check(L.spt_scene_render_async(sc.handle, C.byref(cam), f.col.data_ptr(), f.seeds.data_ptr(),
-                                              f.seeds.data_ptr(), f.px.data_ptr(), w, h, 0, h, 2, 2, 0,
-                                              f.cnt.data_ptr(), st))
-        else:
-            d = torch.tensor(lst, dtype=torch.int32, device=dev)
-            rt.check(L.spt_scene_render_list_async(sc.handle, C.byref(cam), f.col.data_ptr(), seeds0.data_ptr(),
-                                                   f.seeds.data_ptr(), f.px.data_ptr(), w, h, d.data_ptr(),
-                                                   len(lst), 0, 2, 0, f.cnt.data_ptr(), None, st))
-            rt.check(L.spt_scene_render_list_async(sc.handle, C.byref(cam), f.col.data_ptr(), f.seeds.data_ptr(),
-                                                   f.seeds.data_ptr(), f.px.data_ptr(), w, h, d.data_ptr(),
-                                                   len(lst), 2, 2, 0, f.cnt.data_ptr(),
-                                                   cost.data_ptr() if cost is not None else None, st))
+        f = new_frame()
+        d = None if lst is None else torch.tensor(lst, dtype=torch.int32, device=dev)
+        f.render(2, counted=True, groups=d)
+        f.render(2, first_sample=2, counted=True, groups=d, cost=cost, seeds_in=f.seeds)
         torch.cuda.synchronize()
         return f
 
     ref = frame(None)
     rng = np.random.default_rng(5)
     base = [int(g) for g in rng.permutation(ng)]
-    assert frame(base).same(ref, torch)
+    assert frame(base).same_bits(ref)
     cover = base[: ng // 2]                        # half the frame, then repeats (a list is <= ng long)
     lst = cover + [int(g) for g in rng.choice(cover, ng // 4)] + [-1, ng]
     rng.shuffle(lst)
@@ -208,7 +151,7 @@ def test_list_repeated_entries_render_once(rt, kind):
     c2 = torch.zeros(ng, dtype=torch.int32, device=dev)
     once = frame(cover, c1)
     got = frame(lst, c2)
-    assert got.same(once, torch) and got.cnt.tolist() == once.cnt.tolist()
+    assert got.same_bits(once) and got.counters.tolist() == once.counters.tolist()
     if kind == "complex":                     # costs are recorded by the hierarchy kernels
         a, b = c1.cpu().numpy().astype(np.float64)[cover], c2.cpu().numpy().astype(np.float64)[cover]
         assert (a > 0).all() and (b > 0).all()
@@ -255,25 +198,16 @@ def test_count_rays_mode(rt, monkeypatch, kind, env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     w, h = 240, 136
-    S, n, cam = _scene(rt, kind, w, h)
-    sc = rt.SmallptScene(S, n)
-    dev = torch.device("cuda", 0)
-    seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    L = rt.lib()
+    sc, frame = _open(rt, kind, w, h)
     fr = []
     for mode in (0, rt.SPT_COUNT_RAYS, rt.SPT_COUNT_RAYS | rt.SPT_DIRECT_LIGHTING, rt.SPT_DIRECT_LIGHTING):
-        f = _Frame(torch, dev, w, h, seeds0)
-        f.cnt[2] = -1
-        rt.check(L.spt_scene_render_async(sc.handle, C.byref(cam), f.col.data_ptr(), seeds0.data_ptr(),
-                                          f.seeds.data_ptr(), f.px.data_ptr(), w, h, 0, h, 0, 3, mode,
-                                          f.cnt.data_ptr(), st))
+        f = frame()
+        f.counters[2] = -1
+        f.render(3, mode=mode, counted=True)
         torch.cuda.synchronize()
         fr.append(f)
     for a, b in ((fr[0], fr[1]), (fr[3], fr[2])):
-        assert a.same(b, torch)
-        ca, cb = a.cnt.tolist(), b.cnt.tolist()
+        assert a.same_bits(b)
+        ca, cb = a.counters.tolist(), b.counters.tolist()
         assert (ca[0], ca[1], ca[3]) == (cb[0], cb[1], cb[3]) and cb[2] == -1 and ca[2] > 0, (ca, cb)
-    assert L.spt_scene_render_async(sc.handle, C.byref(cam), fr[0].col.data_ptr(), seeds0.data_ptr(),
-                                    fr[0].seeds.data_ptr(), fr[0].px.data_ptr(), w, h, 0, h, 0, 1, 0x400, None,
-                                    st) == rt._lib.RT_ERR_INVALID      # (0x200 is SPT_COST_MAX)
+    assert fr[0].render(1, mode=0x400, check=False) == rt._lib.RT_ERR_INVALID      # (0x200 is SPT_COST_MAX)

@@ -6,14 +6,12 @@ with N bands on a one-GPU box exactly as it runs over N GPUs; with distinct
 devices the gather is an RCCL group (RT_SPT_GATHER=rccl forces that path even
 for one band).  Every result must equal the single-GPU frame bit for bit,
 which the other GPU tests pin to the reference."""
-import json
-import os
-
 import numpy as np
 import pytest
 
+from spt_check import assert_same as _same, golden
+
 pytestmark = pytest.mark.gpu
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "known_answers.json")
 
 
 def _frame(rt, w, h, spp, devices=None, first=0, counters=True):
@@ -22,11 +20,6 @@ def _frame(rt, w, h, spp, devices=None, first=0, counters=True):
         f.render(first, counters=False)
     f.render(spp, counters=counters, devices=devices)
     return f
-
-
-def _same(a, b):
-    assert (a.colors.view(np.uint32) == b.colors.view(np.uint32)).all()
-    assert (a.seeds == b.seeds).all() and (a.pixels == b.pixels).all()
 
 
 def test_render_multi_one_device_equals_single(rt):
@@ -130,8 +123,7 @@ def test_multi_scene_update(rt):
     """spt_multi_set_scene (ReInitSceneGPU) re-uploads the edited scene to
     every band."""
     w, h = 160, 120
-    S, n = rt.scenes.cornell()
-    cam = rt.scenes.cornell_camera(w, h)
+    S, n, cam = rt.scenes.smallpt("cornell", w, h)
     m = rt.SmallptMulti(w, h, [0, 0], S, n)
     m.upload(rt.scenes.seeds(w, h))
     m.render(cam, 0, 2)
@@ -152,7 +144,7 @@ def test_render_multi_full_frame_golden(rt, oracle):
     """BASELINE configs[3]'s frame (Cornell 1920x1080, 64 spp) in eight row
     bands on one device (the N = 8 decomposition), against the reference-
     core golden hashes."""
-    ka = json.load(open(GOLDEN))["smallpt"]["1920x1080_64spp"]
+    ka = golden("1920x1080_64spp")
     f = _frame(rt, 1920, 1080, 64, devices=[0] * 8, counters=False)
     assert oracle.fnv1a64(f.colors) == ka["colors"]
     assert oracle.fnv1a64(f.pixels) == ka["pixels"]
@@ -172,32 +164,15 @@ def test_interleaved_groups_partition_the_frame(rt, ngroups, w, h, spp):
     """spt_scene_render_groups_async for groups 0..ngroups-1 (the interleaved
     multi-GPU split of bench.py) into one device frame == one full-frame
     render, bit for bit, counters summed."""
-    import ctypes as C
     import torch
-    dev = torch.device("cuda", 0)
-    S, n = rt.scenes.cornell()
-    cam = rt.scenes.cornell_camera(w, h)
+    S, n, cam = rt.scenes.smallpt("cornell", w, h)
     sc = rt.SmallptScene(S, n)
-    seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(dev)
-    L = rt.lib()
-    st = torch.cuda.current_stream(dev)
-
-    def buffers():
-        return (torch.zeros(3 * w * h, dtype=torch.float32, device=dev), torch.empty_like(seeds0),
-                torch.zeros(w * h, dtype=torch.int32, device=dev), torch.zeros(4, dtype=torch.int64, device=dev))
-
-    c1, s1, p1, n1 = buffers()
-    rt.check(L.spt_scene_render_async(sc.handle, C.byref(cam), c1.data_ptr(), seeds0.data_ptr(), s1.data_ptr(),
-                                      p1.data_ptr(), w, h, 0, h, 0, spp, 0, n1.data_ptr(), st.cuda_stream))
-    c2, s2, p2, n2 = buffers()
+    one, parts = rt.SmallptDeviceFrame(sc, cam, w, h), rt.SmallptDeviceFrame(sc, cam, w, h)
+    one.render(spp, counted=True)
     for g in range(ngroups):
-        rt.check(L.spt_scene_render_groups_async(sc.handle, C.byref(cam), c2.data_ptr(), seeds0.data_ptr(),
-                                                 s2.data_ptr(), p2.data_ptr(), w, h, g, ngroups, 0, spp, 0,
-                                                 n2.data_ptr(), st.cuda_stream))
+        parts.render(spp, counted=True, share=(g, ngroups))
     torch.cuda.synchronize()
-    assert torch.equal(c1.view(torch.int32), c2.view(torch.int32))
-    assert torch.equal(s1, s2) and torch.equal(p1, p2)
-    assert n1.tolist() == n2.tolist()
-    assert rt.lib().spt_scene_render_groups_async(sc.handle, C.byref(cam), c2.data_ptr(), seeds0.data_ptr(),
-                                                  s2.data_ptr(), p2.data_ptr(), w, h, ngroups, ngroups, 0, 1, 0,
-                                                  None, st.cuda_stream) == rt._lib.RT_ERR_INVALID
+    assert torch.equal(one.colors.view(torch.int32), parts.colors.view(torch.int32))
+    assert torch.equal(one.seeds, parts.seeds) and torch.equal(one.pixels, parts.pixels)
+    assert one.counters.tolist() == parts.counters.tolist()
+    assert parts.render(1, share=(ngroups, ngroups), check=False) == rt._lib.RT_ERR_INVALID

@@ -19,7 +19,6 @@ several GPUs runs the multi-device code automatically:
 
 N = min(8, device count).  The one-GPU repeated-device forms of the same
 code are in test_gpu_multi.py / test_gpu_lists.py."""
-import ctypes as C
 import json
 import os
 import socket
@@ -100,33 +99,18 @@ def test_configs4_lists_distinct_devices_golden(rt, oracle):
     n = _ndev(rt)
     g = GOLDEN["1920x1080_64spp_complex10k"]
     w, h = 1920, 1080
-    S, ns, cam = rt.scenes.complex10k()
-    rt.scenes.update_camera(cam, w, h)
-    L = rt.lib()
+    S, ns, cam = rt.scenes.smallpt("complex", w, h)
     ng = rd.group_count(w, h)
-    seeds_host = rt.scenes.seeds(w, h)
     per = []
     for k in range(n):
         rt.set_device(k)
-        dev = torch.device("cuda", k)
-        with torch.cuda.device(dev):
-            per.append({"dev": dev, "sc": rt.SmallptScene(S, ns),
-                        "seeds0": torch.from_numpy(seeds_host.view(np.int32)).to(dev),
-                        "col": torch.zeros(3 * w * h, dtype=torch.float32, device=dev),
-                        "px": torch.zeros(w * h, dtype=torch.int32, device=dev),
-                        "cost": torch.zeros(ng, dtype=torch.int32, device=dev),
-                        "st": torch.cuda.current_stream(dev)})
-    for p in per:
-        p["seeds"] = torch.empty_like(p["seeds0"])
+        with torch.cuda.device(k):
+            f = rt.SmallptDeviceFrame(rt.SmallptScene(S, ns), cam, w, h, device=k)
+            per.append({"dev": f.device, "frame": f, "cost": torch.zeros(ng, dtype=torch.int32, device=f.device)})
 
     def render(k, lst, cost=None):
-        p = per[k]
         rt.set_device(k)
-        rt.check(L.spt_scene_render_list_async(p["sc"].handle, C.byref(cam), p["col"].data_ptr(),
-                                               p["seeds0"].data_ptr(), p["seeds"].data_ptr(), p["px"].data_ptr(),
-                                               w, h, lst.data_ptr(), lst.numel(), 0, 64, rt.SPT_PATH_TRACING, None,
-                                               cost.data_ptr() if cost is not None else None,
-                                               p["st"].cuda_stream))
+        per[k]["frame"].render(64, mode=rt.SPT_PATH_TRACING, groups=lst, cost=cost)
 
     lists0 = [torch.tensor(rd.interleaved_groups(k, n, w, h), dtype=torch.int32, device=per[k]["dev"])
               for k in range(n)]
@@ -149,9 +133,8 @@ def test_configs4_lists_distinct_devices_golden(rt, oracle):
         sl = rd.group_slots(parts[k], w, h)
         sl = sl[sl >= 0]                                # flipped slots (h-y-1)*w + x
         pi = (h - 1 - sl // w) * w + sl % w             # pixel index y*w + x
-        c = per[k]["col"].cpu().numpy().reshape(-1, 3)
-        s = per[k]["seeds"].cpu().numpy().view(np.uint32).reshape(-1, 2)
-        p = per[k]["px"].cpu().numpy().view(np.uint32)
+        c, s, p = per[k]["frame"].host()
+        c, s = c.reshape(-1, 3), s.reshape(-1, 2)
         col.reshape(-1, 3)[sl] = c[sl]
         seeds.reshape(-1, 2)[sl] = s[sl]
         px[pi] = p[pi]
@@ -160,7 +143,7 @@ def test_configs4_lists_distinct_devices_golden(rt, oracle):
 
 
 WORKER = r'''
-import ctypes as C, json, os, sys
+import json, os, sys
 sys.path[:0] = [%(pkg)r, %(tests)r]
 import numpy as np, torch, torch.distributed as dist
 import oracle_lib as O
@@ -174,9 +157,6 @@ rtamd.set_device(rank)
 L = rtamd.lib()
 G = json.load(open(%(golden)r))["smallpt"]
 W, H, SPP = 1920, 1080, 64
-s = torch.cuda.current_stream(dev)
-seeds0 = torch.from_numpy(rtamd.scenes.seeds(W, H).view(np.int32)).to(dev)
-seeds = torch.empty_like(seeds0)
 ok = True
 
 def pack(col, px):
@@ -189,31 +169,25 @@ def check(col, px, key):
     return got == (G[key]["colors"], G[key]["pixels"])
 
 # (1) Cornell, interleaved 8-row groups + GroupGather (bench.py's headline split)
-S, n = rtamd.scenes.cornell()
-cam = rtamd.scenes.cornell_camera(W, H)
+S, n, cam = rtamd.scenes.smallpt("cornell", W, H)
 sc = rtamd.SmallptScene(S, n)
-col = torch.zeros(3 * W * H, dtype=torch.float32, device=dev)
-px = torch.zeros(W * H, dtype=torch.int32, device=dev)
-rtamd.check(L.spt_scene_render_groups_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                            seeds.data_ptr(), px.data_ptr(), W, H, rank, world, 0, SPP, 0, None,
-                                            s.cuda_stream))
+f = rtamd.SmallptDeviceFrame(sc, cam, W, H, device=rank)
+col, px = f.colors, f.pixels
+f.render(SPP, share=(rank, world))
 rd.GroupGather(col, px, rank, world, W, H, pack=pack(col, px)).gather()
 ok = ok and check(col, px, "1920x1080_64spp")
 print("RANK", rank, "groups", ok, flush=True)
 
 # (2) configs[4], cost-balanced lists + ListGather (bench.py's configs4_tiled split)
-S4, n4, cam4 = rtamd.scenes.complex10k()
-rtamd.scenes.update_camera(cam4, W, H)
+S4, n4, cam4 = rtamd.scenes.smallpt("complex", W, H)
 sc4 = rtamd.SmallptScene(S4, n4)
+f.scene, f.camera = sc4, cam4                   # (the same buffers for the second scene)
 ng = rd.group_count(W, H)
 cost = torch.zeros(ng, dtype=torch.int32, device=dev)
 col.zero_(); px.zero_()
 
 def render(lst, cost_buf=None):
-    rtamd.check(L.spt_scene_render_list_async(sc4.handle, C.byref(cam4), col.data_ptr(), seeds0.data_ptr(),
-                                              seeds.data_ptr(), px.data_ptr(), W, H, lst.data_ptr(), lst.numel(),
-                                              0, SPP, 0, None, cost_buf.data_ptr() if cost_buf is not None else None,
-                                              s.cuda_stream))
+    f.render(SPP, groups=lst, cost=cost_buf)
 
 render(torch.tensor(rd.interleaved_groups(rank, world, W, H), dtype=torch.int32, device=dev), cost)
 costs = cost.to(torch.int64)

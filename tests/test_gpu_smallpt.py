@@ -6,35 +6,16 @@ the integer pixels and RNG state must match exactly."""
 import numpy as np
 import pytest
 
+from spt_check import assert_same, golden, oracle_frame as _oracle_frame
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
 
 
-def _oracle_frame(oracle, w, h, steps, mode=0, spheres=None, cam=None):
-    S, n = oracle.cornell() if spheres is None else spheres
-    cam = oracle.cornell_camera(w, h) if cam is None else cam
-    col = np.zeros(3 * w * h, np.float32)
-    seeds = oracle.seeds(w, h)
-    px = np.zeros(w * h, np.uint32)
-    first = 0
-    cnt = [0, 0, 0, 0]
-    for k in steps:
-        c = oracle.smallpt_render(S, n, cam, col, seeds, px, w, h, first, k, dl=mode, nthreads=8)
-        cnt = [a + b for a, b in zip(cnt, c)]
-        first += k
-    return col, seeds, px, cnt
-
-
 def _check(got, ref):
-    gcol, gseeds, gpx, gcnt = got
-    rcol, rseeds, rpx, rcnt = ref
-    err = np.abs(gcol.astype(np.float64) - rcol.astype(np.float64))
+    err = np.abs(got[0].astype(np.float64) - ref[0].astype(np.float64))
     assert err.max() <= TOL, "max |dHDR| %g" % err.max()
-    assert (gcol.view(np.uint32) == rcol.view(np.uint32)).all(), "HDR not bit-exact (%d slots)" % (
-        (gcol != rcol).sum())
-    assert (gseeds == rseeds).all()
-    assert (gpx == rpx).all()
-    assert gcnt == rcnt, (gcnt, rcnt)
+    assert_same(got, ref, counted=True)      # ... and bit-exact, with seeds, pixels and the four counters
 
 
 @pytest.mark.parametrize("w,h,steps", [(640, 480, [1]), (640, 480, [1, 3]), (160, 120, [8, 8])])
@@ -66,10 +47,7 @@ def test_batching_is_exact(rt):
 # / configs[3] frames.
 @pytest.mark.parametrize("key", ["1024x768_64spp", "1920x1080_64spp", "1920x1080_256spp"])
 def test_full_size_golden(rt, oracle, key):
-    import json
-    import os
-    gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "known_answers.json")))
-    g = gold["smallpt"][key]
+    g = golden(key)
     res, spp = key.split("_")
     w, h = map(int, res.split("x"))
     f = rt.SmallptFrame(w, h)
@@ -95,19 +73,18 @@ def test_generic_lds_path(rt, oracle):
     w, h = 128, 96
     f = rt.SmallptFrame(w, h, spheres=spheres, nspheres=n)
     f.render(3)
-    ref = _oracle_frame(oracle, w, h, [3], spheres=(spheres, n))
+    ref = _oracle_frame(oracle, w, h, [3], scene=(spheres, n))
     _check((f.colors, f.seeds, f.pixels, f.counters), ref)
 
 
 def test_large_scene_hierarchy_vs_oracle(rt, oracle):
     """configs[4] scene (10k spheres, >= 256: the exact-culling hierarchy
     path) against the oracle's full scan, small frame."""
-    spheres, n, cam = rt.scenes.complex10k()
     w, h = 48, 32
-    rt.scenes.update_camera(cam, w, h)
+    spheres, n, cam = rt.scenes.smallpt("complex", w, h)
     f = rt.SmallptFrame(w, h, spheres=spheres, nspheres=n, camera=cam)
     f.render(1)
-    ref = _oracle_frame(oracle, w, h, [1], spheres=(spheres, n), cam=cam)
+    ref = _oracle_frame(oracle, w, h, [1], scene=(spheres, n), cam=cam)
     _check((f.colors, f.seeds, f.pixels, f.counters), ref)
 
 
@@ -117,14 +94,13 @@ def test_nonstandard_refl_takes_refr_branch(rt, oracle, nonstd):
     the REFR branch.  A hierarchy scene (configs[4]'s spheres, all DIFF, so
     normally run with the light-only pass A) with some spheres set to a
     non-standard refl must still refract there, as the oracle does."""
-    spheres, n, cam = rt.scenes.complex10k()
+    w, h = 48, 32
+    spheres, n, cam = rt.scenes.smallpt("complex", w, h)
     for i in range(2, n, 5):                 # (0: the light, 1: the ground)
         spheres[i].refl = nonstd
-    w, h = 48, 32
-    rt.scenes.update_camera(cam, w, h)
     f = rt.SmallptFrame(w, h, spheres=spheres, nspheres=n, camera=cam)
     f.render(2)
-    ref = _oracle_frame(oracle, w, h, [2], spheres=(spheres, n), cam=cam)
+    ref = _oracle_frame(oracle, w, h, [2], scene=(spheres, n), cam=cam)
     _check((f.colors, f.seeds, f.pixels, f.counters), ref)
 
 
@@ -135,16 +111,11 @@ def test_large_scene_global_path(rt, oracle, env, monkeypatch):
     the 10k configs[4] scene with the hierarchy disabled, and Cornell."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    if "RT_SPT_NO_BVH" in env:
-        spheres, n, cam = rt.scenes.complex10k()
-        w, h = 32, 24
-        rt.scenes.update_camera(cam, w, h)
-    else:
-        (spheres, n), w, h = rt.scenes.cornell(), 96, 64
-        cam = rt.scenes.cornell_camera(w, h)
+    kind, w, h = ("complex", 32, 24) if "RT_SPT_NO_BVH" in env else ("cornell", 96, 64)
+    spheres, n, cam = rt.scenes.smallpt(kind, w, h)
     f = rt.SmallptFrame(w, h, spheres=spheres, nspheres=n, camera=cam)
     f.render(2)
-    ref = _oracle_frame(oracle, w, h, [2], spheres=(spheres, n), cam=cam)
+    ref = _oracle_frame(oracle, w, h, [2], scene=(spheres, n), cam=cam)
     _check((f.colors, f.seeds, f.pixels, f.counters), ref)
 
 
@@ -162,15 +133,11 @@ def test_configs4_full_size_golden(rt, oracle, counted, walk, monkeypatch):
     kernel (with and without the work counters), against the golden hashes of
     the reference's own full-scan core (tests/golden/make_golden_c4.py,
     oracle/_ref: geomfunc.h:71-110 Intersect / IntersectP)."""
-    import json
-    import os
     for k, v in walk.items():
         monkeypatch.setenv(k, v)
-    gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "known_answers.json")))
-    g = gold["smallpt"]["1920x1080_64spp_complex10k"]
-    spheres, n, cam = rt.scenes.complex10k()
+    g = golden("1920x1080_64spp_complex10k")
     w, h = 1920, 1080
-    rt.scenes.update_camera(cam, w, h)
+    spheres, n, cam = rt.scenes.smallpt("complex", w, h)
     for frame in range(3):          # (the 1st launch of the key learns its order, later ones use it)
         f = rt.SmallptFrame(w, h, spheres=spheres, nspheres=n, camera=cam)
         f.render(64, counters=counted)
@@ -191,14 +158,10 @@ def test_configs4_cooperative_walk_golden(rt, oracle, counted, tune, monkeypatch
     two-lane ones).  Every frame must equal the reference core's golden
     hashes (configs[4], 1920x1080, 64 spp), counted (and the counters exact)
     and uncounted."""
-    import json
-    import os
     monkeypatch.setenv("RT_SPT_TUNE", tune)
-    gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "known_answers.json")))
-    g = gold["smallpt"]["1920x1080_64spp_complex10k"]
-    spheres, n, cam = rt.scenes.complex10k()
+    g = golden("1920x1080_64spp_complex10k")
     w, h = 1920, 1080
-    rt.scenes.update_camera(cam, w, h)
+    spheres, n, cam = rt.scenes.smallpt("complex", w, h)
     first = None
     for i in range(3):
         f = rt.SmallptFrame(w, h, spheres=spheres, nspheres=n, camera=cam)
@@ -222,32 +185,21 @@ def test_configs4_rank_shares_golden(rt, oracle, nranks):
     the later frames use the window class's default cooperative tier (two
     lanes per pixel at N = 2, four at N = 4, eight at N = 8).  The assembled
     frame of the third round equals the reference core's golden hashes."""
-    import ctypes as C
-    import json
-    import os
     import torch
-    gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "known_answers.json")))
-    g = gold["smallpt"]["1920x1080_64spp_complex10k"]
-    spheres, n, cam = rt.scenes.complex10k()
+    g = golden("1920x1080_64spp_complex10k")
     w, h = 1920, 1080
-    rt.scenes.update_camera(cam, w, h)
-    dev = torch.device("cuda", 0)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    L = rt.lib()
-    seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(dev)
+    spheres, n, cam = rt.scenes.smallpt("complex", w, h)
     scenes = [rt.SmallptScene(spheres, n) for _ in range(nranks)]
     try:
+        f = rt.SmallptDeviceFrame(scenes[0], cam, w, h)
         for _ in range(3):                     # learn, then the learnt order and its tiers
-            col = torch.zeros(3 * w * h, dtype=torch.float32, device=dev)
-            seeds = torch.zeros_like(seeds0)
-            px = torch.zeros(w * h, dtype=torch.int32, device=dev)
+            f.reset()
             for k, sc in enumerate(scenes):
-                rt.check(L.spt_scene_render_groups_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                                         seeds.data_ptr(), px.data_ptr(), w, h, k, nranks, 0, 64, 0,
-                                                         None, st))
+                f.scene = sc                   # (one frame, each share from its own scene)
+                f.render(64, share=(k, nranks))
             torch.cuda.synchronize()
-        got = (oracle.fnv1a64(col.cpu().numpy()), oracle.fnv1a64(px.cpu().numpy().view(np.uint32)),
-               oracle.fnv1a64(seeds.cpu().numpy().view(np.uint32)))
+        col, seeds, px = f.host()
+        got = (oracle.fnv1a64(col), oracle.fnv1a64(px), oracle.fnv1a64(seeds))
         assert got == (g["colors"], g["pixels"], g["seeds"])
     finally:
         for sc in scenes:
@@ -260,29 +212,21 @@ def test_async_device_paths(rt, oracle):
     import ctypes as C
     import torch
     w, h = 96, 64
-    S, n = rt.scenes.cornell()
-    cam = rt.scenes.cornell_camera(w, h)
-    dev = torch.device("cuda", 0)
-    seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(dev)
-    outs = []
-    for use_scene in (True, False):
-        col = torch.zeros(3 * w * h, dtype=torch.float32, device=dev)
-        seeds = torch.zeros_like(seeds0)
-        px = torch.zeros(w * h, dtype=torch.int32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        if use_scene:
-            sc = rt.SmallptScene(S, n)
-            for r0, r1 in ((0, 40), (40, h)):
-                rt.check(rt.lib().spt_scene_render_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                                         seeds.data_ptr(), px.data_ptr(), w, h, r0, r1, 0, 2, 0,
-                                                         None, st))
-        else:
-            d_s = torch.frombuffer(bytearray(bytes(S)), dtype=torch.uint8).to(dev)
-            for r0, r1 in ((0, 40), (40, h)):
-                rt.check(rt.lib().spt_render_async(d_s.data_ptr(), n, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                                   seeds.data_ptr(), px.data_ptr(), w, h, r0, r1, 0, 2, 0, None, st))
-        torch.cuda.synchronize()
-        outs.append((col.cpu().numpy(), seeds.cpu().numpy().view(np.uint32), px.cpu().numpy().view(np.uint32)))
+    S, n, cam = rt.scenes.smallpt("cornell", w, h)
+    sc = rt.SmallptScene(S, n)
+    f = rt.SmallptDeviceFrame(sc, cam, w, h)
+    for rows in ((0, 40), (40, h)):
+        f.render(2, rows=rows)
+    outs = [f.host()]
+    dev, seeds0 = f.device, f.seeds0
+    col, seeds, px = torch.zeros_like(f.colors), torch.zeros_like(seeds0), torch.zeros_like(f.pixels)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    d_s = torch.frombuffer(bytearray(bytes(S)), dtype=torch.uint8).to(dev)
+    for r0, r1 in ((0, 40), (40, h)):
+        rt.check(rt.lib().spt_render_async(d_s.data_ptr(), n, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
+                                           seeds.data_ptr(), px.data_ptr(), w, h, r0, r1, 0, 2, 0, None, st))
+    torch.cuda.synchronize()
+    outs.append((col.cpu().numpy(), seeds.cpu().numpy().view(np.uint32), px.cpu().numpy().view(np.uint32)))
     ref = _oracle_frame(oracle, w, h, [2])
     for col, seeds, px in outs:
         assert (col.view(np.uint32) == ref[0].view(np.uint32)).all()
@@ -297,8 +241,7 @@ def test_scene_cache_follows_the_array(rt, oracle):
     import ctypes as C
     import torch
     w, h = 64, 48
-    S, n = rt.scenes.cornell()
-    cam = rt.scenes.cornell_camera(w, h)
+    S, n, cam = rt.scenes.smallpt("cornell", w, h)
     T, _ = rt.scenes.cornell()
     T[7].c.x, T[8].p.y = 0.25, T[8].p.y + 3.0
     dev = torch.device("cuda", 0)
@@ -306,7 +249,7 @@ def test_scene_cache_follows_the_array(rt, oracle):
     d_s = torch.frombuffer(bytearray(bytes(S)), dtype=torch.uint8).to(dev)
     st = torch.cuda.current_stream(dev).cuda_stream
     for arr in (S, S, T, S):
-        ref_col, ref_seeds, ref_px, _ = _oracle_frame(oracle, w, h, [2], spheres=(arr, n), cam=cam)
+        ref_col, ref_seeds, ref_px, _ = _oracle_frame(oracle, w, h, [2], scene=(arr, n), cam=cam)
         d_s.copy_(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8))     # same pointer, new contents
         col = torch.zeros(3 * w * h, dtype=torch.float32, device=dev)
         seeds = torch.zeros_like(seeds0)
@@ -329,31 +272,19 @@ def test_adaptive_group_order_is_exact(rt, monkeypatch, sched, walk):
     key records, the 2nd builds the order, the 3rd and later use it.  Every
     launch must give the same bits as the plain dispatch (RT_SPT_SCHED=0),
     counted and uncounted, full frame and a row window."""
-    import ctypes as C
-    import torch
     monkeypatch.setenv("RT_SPT_SCHED", sched)
     for k, v in walk.items():
         monkeypatch.setenv(k, v)
     w, h = 480, 270
-    spheres, n, cam = rt.scenes.complex10k()
-    rt.scenes.update_camera(cam, w, h)
+    spheres, n, cam = rt.scenes.smallpt("complex", w, h)
     sc = rt.SmallptScene(spheres, n)
-    dev = torch.device("cuda", 0)
-    seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+    f = rt.SmallptDeviceFrame(sc, cam, w, h)
     outs = []
-    for r0, r1 in ((0, h), (0, h), (0, h), (0, h), (40, 200), (40, 200), (40, 200)):
+    for rows in ((0, h), (0, h), (0, h), (0, h), (40, 200), (40, 200), (40, 200)):
         for counted in (False, True):
-            col = torch.zeros(3 * w * h, dtype=torch.float32, device=dev)
-            seeds = torch.zeros_like(seeds0)
-            px = torch.zeros(w * h, dtype=torch.int32, device=dev)
-            cnt = torch.zeros(4, dtype=torch.int64, device=dev)
-            rt.check(rt.lib().spt_scene_render_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                                     seeds.data_ptr(), px.data_ptr(), w, h, r0, r1, 0, 3, 0,
-                                                     cnt.data_ptr() if counted else None, st))
-            torch.cuda.synchronize()
-            outs.append(((r0, r1), col.cpu().numpy().view(np.uint32), seeds.cpu().numpy(), px.cpu().numpy(),
-                         cnt.cpu().numpy() if counted else None))
+            f.reset().render(3, rows=rows, counted=counted)
+            col, seeds, px = f.host()
+            outs.append((rows, col.view(np.uint32), seeds, px, f.counters.cpu().numpy() if counted else None))
     ref = {}
     for key, c, s_, p, k in outs:
         if key not in ref:
@@ -371,47 +302,29 @@ def test_graph_replay_survives_order_changes(rt):
     -- must neither rewrite nor free it.  Capture a launch of a small window
     once its order is in use, run two larger keys until theirs are, replay:
     the bits equal an uncaptured launch of the small window."""
-    import ctypes as C
     import torch
     w, h = 480, 270
-    spheres, n, cam = rt.scenes.complex10k()
-    rt.scenes.update_camera(cam, w, h)
+    spheres, n, cam = rt.scenes.smallpt("complex", w, h)
     sc = rt.SmallptScene(spheres, n)
-    dev = torch.device("cuda", 0)
-    seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(dev)
-
-    def bufs():
-        return (torch.zeros(3 * w * h, dtype=torch.float32, device=dev), torch.zeros_like(seeds0),
-                torch.zeros(w * h, dtype=torch.int32, device=dev))
-
-    def launch(r0, r1, spp, b, stream):
-        col, seeds, px = b
-        rt.check(rt.lib().spt_scene_render_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                                 seeds.data_ptr(), px.data_ptr(), w, h, r0, r1, 0, spp, 0, None,
-                                                 stream))
-
-    cur = torch.cuda.current_stream(dev).cuda_stream
-    small = (96, 144, 2)
+    tmp, gb, ref = (rt.SmallptDeviceFrame(sc, cam, w, h) for _ in range(3))
+    small = {"nsamples": 2, "rows": (96, 144)}
     for _ in range(3):                               # record, build the order, use it
-        launch(*small, bufs(), cur)
+        tmp.render(**small)
     torch.cuda.synchronize()
-    gb = bufs()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, capture_error_mode="relaxed"):
-        launch(*small, gb, torch.cuda.current_stream(dev).cuda_stream)
+        gb.render(**small)                           # (on the capture's side stream: the current one in here)
     torch.cuda.synchronize()
-    for key in ((0, h, 2), (0, h, 3)):               # new keys, larger order buffers
+    for spp in (2, 3):                               # new keys, larger order buffers
         for _ in range(3):
-            launch(*key, bufs(), cur)
+            tmp.render(spp)
     torch.cuda.synchronize()
-    for t in gb:
-        t.zero_()
+    gb.reset()
     g.replay()
-    ref = bufs()
-    launch(*small, ref, cur)
+    ref.render(**small)
     torch.cuda.synchronize()
-    for a, b in zip(gb, ref):
-        assert (a.cpu().numpy().view(np.uint32) == b.cpu().numpy().view(np.uint32)).all()
+    for a, b in zip(gb.host(), ref.host()):
+        assert (a.view(np.uint32) == b.view(np.uint32)).all()
 
 
 def test_capture_limit_and_release(rt):
@@ -420,22 +333,14 @@ def test_capture_limit_and_release(rt):
     next launch is refused (RT_ERR_INVALID, nothing launched); once the graph
     is destroyed spt_scene_release_captures hands the entries out again, and
     a new capture replays to the uncaptured frame's bits."""
-    import ctypes as C
     import torch
     w, h = 64, 16
-    spheres, n, cam = rt.scenes.complex10k()
-    rt.scenes.update_camera(cam, w, h)
+    spheres, n, cam = rt.scenes.smallpt("complex", w, h)
     sc = rt.SmallptScene(spheres, n)
-    dev = torch.device("cuda", 0)
-    seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(dev)
-    L = rt.lib()
-    b = (torch.zeros(3 * w * h, dtype=torch.float32, device=dev), torch.zeros_like(seeds0),
-         torch.zeros(w * h, dtype=torch.int32, device=dev))
+    b, gb, ref = (rt.SmallptDeviceFrame(sc, cam, w, h) for _ in range(3))
 
-    def launch(buf):
-        return L.spt_scene_render_async(sc.handle, C.byref(cam), buf[0].data_ptr(), seeds0.data_ptr(),
-                                        buf[1].data_ptr(), buf[2].data_ptr(), w, h, 0, h, 0, 1, 0, None,
-                                        torch.cuda.current_stream(dev).cuda_stream)
+    def launch(f):
+        return f.render(1, check=False)
 
     for _ in range(3):
         rt.check(launch(b))
@@ -450,18 +355,15 @@ def test_capture_limit_and_release(rt):
     assert launch(b) == rt._lib.RT_ERR_INVALID        # (uncaptured launches need an entry too)
     del g, g2
     torch.cuda.synchronize()
-    rt.check(L.spt_scene_release_captures(sc.handle))
-    gb = tuple(torch.zeros_like(t) for t in b)
+    rt.check(rt.lib().spt_scene_release_captures(sc.handle))
     g3 = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g3, capture_error_mode="relaxed"):
         rt.check(launch(gb))
     g3.replay()
-    ref = tuple(torch.zeros_like(t) for t in b)
     rt.check(launch(ref))
     torch.cuda.synchronize()
-    for a, r in zip(gb, ref):
+    for a, r in zip((gb.colors, gb.seeds, gb.pixels), (ref.colors, ref.seeds, ref.pixels)):
         assert torch.equal(a.view(torch.int32), r.view(torch.int32))
-
 
 def _bvh_vs_scan(rt, monkeypatch, spheres, n, cam, w, h, spp, mode=0):
     """Renders with the 8-wide hierarchy, the binary hierarchy (RT_SPT_WIDE=0)
@@ -489,8 +391,7 @@ def _bvh_vs_scan(rt, monkeypatch, spheres, n, cam, w, h, spp, mode=0):
 
 def test_bvh_equals_full_scan_configs4(rt, monkeypatch):
     """configs[4] (10k spheres) at 1920x1080, 2 spp: hierarchy == full scan."""
-    spheres, n, cam = rt.scenes.complex10k()
-    rt.scenes.update_camera(cam, 1920, 1080)
+    spheres, n, cam = rt.scenes.smallpt("complex", 1920, 1080)
     _bvh_vs_scan(rt, monkeypatch, spheres, n, cam, 1920, 1080, 2)
 
 
@@ -550,7 +451,7 @@ def test_random_scenes_vs_oracle(rt, oracle, seed):
     f = rt.SmallptFrame(w, h, spheres=S, nspheres=n, camera=cam, mode=mode)
     for k in steps:
         f.render(k)
-    ref = _oracle_frame(oracle, w, h, steps, mode=mode, spheres=(S, n), cam=cam)
+    ref = _oracle_frame(oracle, w, h, steps, mode=mode, scene=(S, n), cam=cam)
     _check((f.colors, f.seeds, f.pixels, f.counters), ref)
     g = rt.SmallptFrame(w, h, spheres=S, nspheres=n, camera=cam, mode=mode)
     for k in steps:
@@ -582,7 +483,7 @@ def test_light_free_scene_vs_oracle(rt, oracle, geo, monkeypatch):
         f = rt.SmallptFrame(w, h, spheres=S, nspheres=n, camera=cam, mode=mode)
         f.render(3)
         _check((f.colors, f.seeds, f.pixels, f.counters),
-               _oracle_frame(oracle, w, h, [3], mode=mode, spheres=(S, n), cam=cam))
+               _oracle_frame(oracle, w, h, [3], mode=mode, scene=(S, n), cam=cam))
 
 
 def test_pack_pixels_matches_render(rt):
@@ -612,8 +513,6 @@ def test_one_and_two_query_iterations(rt, oracle, dual, monkeypatch):
     the two-query iteration (shadow ray + bounce ray together, which the
     library picks for every single-light scene) -- forced either way, against the
     oracle at a small size and the reference-core golden at 1920x1080x64."""
-    import json
-    import os
     monkeypatch.setenv("RT_SPT_DUAL", dual)
     w, h = 200, 150
     f = rt.SmallptFrame(w, h)
@@ -622,8 +521,7 @@ def test_one_and_two_query_iterations(rt, oracle, dual, monkeypatch):
     ref = _oracle_frame(oracle, w, h, [3, 2])
     assert (f.colors.view(np.uint32) == ref[0].view(np.uint32)).all()
     assert (f.seeds == ref[1]).all() and (f.pixels == ref[2]).all()
-    g = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "known_answers.json")))
-    g = g["smallpt"]["1920x1080_64spp"]
+    g = golden("1920x1080_64spp")
     f = rt.SmallptFrame(1920, 1080)
     f.render(64, counters=False)
     assert (oracle.fnv1a64(f.colors), oracle.fnv1a64(f.pixels), oracle.fnv1a64(f.seeds)) == \

@@ -10,8 +10,9 @@ last), progressive launches, every flush threshold from "no batching" to the
 ring's largest, both block shapes and geometry paths, and scenes built to
 force each flush condition (a previous sample still unfolded, no free pending
 slot, an emitter term behind a pending contribution)."""
-import numpy as np
 import pytest
+
+import spt_check
 
 pytestmark = pytest.mark.gpu
 
@@ -19,41 +20,14 @@ DIFF, SPEC, REFR = 0, 1, 2
 SQ_MAX = 49          # sptpolicy::SQ_RING - 63: the largest threshold the ring allows
 
 
-def _oracle(oracle, w, h, steps, scene=None, cam=None):
-    S, n = oracle.cornell() if scene is None else scene
-    cam = oracle.cornell_camera(w, h) if cam is None else cam
-    col = np.zeros(3 * w * h, np.float32)
-    seeds = oracle.seeds(w, h)
-    px = np.zeros(w * h, np.uint32)
-    first = 0
-    for k in steps:
-        oracle.smallpt_render(S, n, cam, col, seeds, px, w, h, first, k, nthreads=8)
-        first += k
-    for a in (col, seeds, px):
-        a.setflags(write=False)
-    return col, seeds, px
-
-
 @pytest.fixture(scope="module")
 def refs(oracle):
     """Oracle Cornell frames, computed once per (w, h, passes), read-only."""
-    cache = {}
-
-    def get(w, h, steps):
-        key = (w, h, tuple(steps))
-        if key not in cache:
-            cache[key] = _oracle(oracle, w, h, steps)
-        return cache[key]
-
-    return get
+    return spt_check.frame_cache(oracle)
 
 
 def _same(f, ref):
-    col, seeds, px = ref
-    bad = (f.colors.view(np.uint32) != col.view(np.uint32)).sum()
-    assert bad == 0, "HDR not bit-exact (%d slots)" % bad
-    assert (f.pixels == px).all()
-    assert (f.seeds == seeds).all()
+    spt_check.assert_same(f, ref, counted=False)      # every launch here is uncounted
 
 
 def _scene(rt, rows):
@@ -128,7 +102,7 @@ def test_open_scene_short_samples(rt, oracle, monkeypatch, tune):
     cam = _camera(rt, w, h, (0.0, 8.0, 40.0), (0.0, 5.0, 0.0))
     f = rt.SmallptFrame(w, h, spheres=S, nspheres=n, camera=cam)
     f.render(8, counters=False)
-    _same(f, _oracle(oracle, w, h, [8], scene=(S, n), cam=cam))
+    _same(f, spt_check.oracle_frame(oracle, w, h, [8], scene=(S, n), cam=cam))
 
 
 @pytest.mark.parametrize("tune", ["", "sq=1", "sq=%d" % SQ_MAX])
@@ -151,7 +125,7 @@ def test_mirror_heavy_scene(rt, oracle, monkeypatch, tune):
     cam = _camera(rt, w, h, (0.0, 10.0, 45.0), (0.0, 6.0, 0.0))
     f = rt.SmallptFrame(w, h, spheres=S, nspheres=n, camera=cam)
     f.render(8, counters=False)
-    _same(f, _oracle(oracle, w, h, [8], scene=(S, n), cam=cam))
+    _same(f, spt_check.oracle_frame(oracle, w, h, [8], scene=(S, n), cam=cam))
 
 
 def test_two_light_scene_keeps_the_one_query_kernel(rt, oracle):
@@ -162,19 +136,11 @@ def test_two_light_scene_keeps_the_one_query_kernel(rt, oracle):
     S, n = _scene(rt, rows)
     f = rt.SmallptFrame(w, h, spheres=S, nspheres=n)
     f.render(3, counters=False)
-    _same(f, _oracle(oracle, w, h, [3], scene=(S, n)))
-    import ctypes as C
+    _same(f, spt_check.oracle_frame(oracle, w, h, [3], scene=(S, n)))
     import torch
     sc = rt.SmallptScene(S, n)
-    dev = torch.device("cuda", 0)
-    col = torch.zeros(3 * w * h, dtype=torch.float32, device=dev)
-    px = torch.zeros(w * h, dtype=torch.int32, device=dev)
-    sin = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32).copy()).to(dev)
-    sout = torch.empty_like(sin)
-    cam = rt.scenes.cornell_camera(w, h)
-    rt.check(rt.lib().spt_scene_render_async(sc.handle, C.byref(cam), col.data_ptr(), sin.data_ptr(), sout.data_ptr(),
-                                             px.data_ptr(), w, h, 0, h, 0, 1, 0, None,
-                                             torch.cuda.current_stream(dev).cuda_stream))
+    f = rt.SmallptDeviceFrame(sc, rt.scenes.cornell_camera(w, h), w, h)
+    f.render(1)
     torch.cuda.synchronize()
     info = sc.info()
     sc.close()

@@ -11,12 +11,11 @@ mode); every comparison is bit for bit -- HDR colours, seeds, pixels, and all
 four counters of a counted launch.  Every case first asserts through
 spt_scene_info (SmallptScene.info) the kernel family, leaf size and tier it
 means to run, so none can pass on another path."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import scenes_layouts as sl
+import spt_check
 
 pytestmark = pytest.mark.gpu
 
@@ -29,7 +28,8 @@ FRAME = (64, 48)        # 24 tiles in six groups: one persistent block
 def world(oracle):
     """Scenes (built once) and oracle frames (computed once per scene, frame,
     window and mode; read-only)."""
-    scenes, frames = {}, {}
+    scenes = {}
+    frames = spt_check.frame_cache(oracle)
 
     def scene(name):
         if name not in scenes:
@@ -48,76 +48,32 @@ def world(oracle):
         return scenes[name]
 
     def ref(name, w, h, mode, rows=None):
-        key = (name, w, h, mode, rows)
-        if key not in frames:
-            S, n, cam = scene(name)
-            col = np.zeros(3 * w * h, np.float32)
-            seeds = oracle.seeds(w, h)
-            px = np.zeros(w * h, np.uint32)
-            r0, r1 = rows or (0, h)
-            cnt = oracle.smallpt_render(S, n, cam(w, h), col, seeds, px, w, h, 0, SPP, row_begin=r0, row_end=r1,
-                                        dl=mode, nthreads=8)
-            for a in (col, seeds, px):
-                a.setflags(write=False)
-            frames[key] = (col, seeds, px, cnt)
-        return frames[key]
+        S, n, cam = scene(name)
+        return frames(w, h, [SPP], mode, rows, name=name, make=lambda: ((S, n), cam(w, h)))
 
     return scene, ref
 
 
 class Launcher:
-    """One prepared scene and device buffers of one frame size."""
+    """One prepared scene and a device frame of one size."""
 
     def __init__(self, rt, S, n, cam, w, h):
         import torch
-        self.rt, self.torch, self.cam, self.w, self.h = rt, torch, cam, w, h
         self.sc = rt.SmallptScene(S, n)
-        self.dev = torch.device("cuda", 0)
-        self.seeds0 = torch.from_numpy(rt.scenes.seeds(w, h).view(np.int32)).to(self.dev)
-        self.all_groups = torch.arange(rt.lib().spt_group_count(w, h), dtype=torch.int32, device=self.dev)
+        self.frame = rt.SmallptDeviceFrame(self.sc, cam, w, h)
+        self.all_groups = torch.arange(self.frame.groups_total, dtype=torch.int32, device=self.frame.device)
 
     def render(self, mode, counted, as_list=False, rows=None):
-        """One launch of SPP samples from the initial state: (colours, seeds,
-        pixels, counters or None).  as_list: the whole frame as a group list
-        without a cost pointer (an order, so the tiers apply)."""
-        torch, rt, w, h = self.torch, self.rt, self.w, self.h
-        col = torch.zeros(3 * w * h, dtype=torch.float32, device=self.dev)
-        seeds = torch.zeros_like(self.seeds0)
-        px = torch.zeros(w * h, dtype=torch.int32, device=self.dev)
-        cnt = torch.zeros(4, dtype=torch.int64, device=self.dev)
-        st = torch.cuda.current_stream(self.dev).cuda_stream
-        cp = cnt.data_ptr() if counted else None
-        L = rt.lib()
-        if as_list:
-            rt.check(L.spt_scene_render_list_async(self.sc.handle, C.byref(self.cam), col.data_ptr(),
-                                                   self.seeds0.data_ptr(), seeds.data_ptr(), px.data_ptr(), w, h,
-                                                   self.all_groups.data_ptr(), len(self.all_groups), 0, SPP, mode, cp,
-                                                   None, st))
-        else:
-            r0, r1 = rows or (0, h)
-            rt.check(L.spt_scene_render_async(self.sc.handle, C.byref(self.cam), col.data_ptr(),
-                                              self.seeds0.data_ptr(), seeds.data_ptr(), px.data_ptr(), w, h, r0, r1, 0,
-                                              SPP, mode, cp, st))
-        torch.cuda.synchronize()
-        return (col.cpu().numpy(), seeds.cpu().numpy().view(np.uint32), px.cpu().numpy().view(np.uint32),
-                cnt.tolist() if counted else None)
+        """One launch of SPP samples from the initial state into the zeroed
+        frame: (colours, seeds, pixels, counters or None).  as_list: the whole
+        frame as a group list without a cost pointer (an order, so the tiers
+        apply)."""
+        f = self.frame.reset()
+        f.render(SPP, mode=mode, counted=counted, rows=rows, groups=self.all_groups if as_list else None)
+        return f.host() + (f.counters.tolist() if counted else None,)
 
     def close(self):
         self.sc.close()
-
-
-def _same(got, ref):
-    """_check of test_gpu_smallpt.py: HDR bits, seeds, pixels, and all four
-    counters of a counted launch."""
-    gcol, gseeds, gpx, gcnt = got
-    rcol, rseeds, rpx, rcnt = ref
-    diff = gcol.view(np.uint32) != rcol.view(np.uint32)
-    assert not diff.any(), "HDR not bit-exact (%d slots, max |d| %g)" % (
-        diff.sum(), np.abs(gcol.astype(np.float64) - rcol).max())
-    assert (gseeds == rseeds).all()
-    assert (gpx == rpx).all()
-    if gcnt is not None:
-        assert gcnt == rcnt, (gcnt, rcnt)
 
 
 def _open(rt, world, name, w, h):
@@ -136,7 +92,7 @@ def _counted_and_uncounted(lz, ref, mode, expect, **kw):
         assert info["launches"] == before + 1
         for k, v in expect.items():
             assert info[k] == v, (k, info)
-        _same(got, ref)
+        spt_check.assert_same(got, ref)     # HDR bits, seeds, pixels, a counted launch's four counters
 
 
 # ---- layouts -------------------------------------------------------------
@@ -222,7 +178,7 @@ def test_cooperative_tier_of_a_learnt_order(rt, world, monkeypatch):
         ref = world[1]("leaf8", w, h, 1)
         for counted in (False, True):
             for i in range(3):
-                _same(lz.render(1, counted), ref)
+                spt_check.assert_same(lz.render(1, counted), ref)
                 info = lz.sc.info()
                 if i == 0:
                     assert info["cg"] == 0 and info["n1"] == 0, info       # no order yet: a lane per pixel
@@ -317,7 +273,6 @@ def test_tiny_frames(rt, world, monkeypatch, w, h, name, env, family):
 def test_tiny_frame_row_window(rt, world, monkeypatch, name, env, family):
     """9x3, rows [1, 2): the window's row equals the oracle's and every
     colour, pixel and seed slot outside it keeps its sentinel."""
-    import torch
     w, h, r0, r1 = 9, 3, 1, 2
     lz = _tiny_open(rt, world, monkeypatch, name, env, family, w, h)
     try:
@@ -329,23 +284,15 @@ def test_tiny_frame_row_window(rt, world, monkeypatch, name, env, family):
             inside[h - r1:h - r0] = True                           # accumulator and seed rows are flipped
             ins = inside.reshape(-1)
             assert (ref[0].view(np.uint32).reshape(-1, 3)[ins] == full[0].view(np.uint32).reshape(-1, 3)[ins]).all()
-            col = torch.full((3 * w * h,), -7.25, dtype=torch.float32, device=lz.dev)
-            px = torch.full((w * h,), 0x25A5A5A5, dtype=torch.int32, device=lz.dev)
-            sout = torch.full((2 * w * h,), 0x5EADBEEF, dtype=torch.int32, device=lz.dev)
-            cnt = torch.zeros(4, dtype=torch.int64, device=lz.dev)
-            st = torch.cuda.current_stream(lz.dev).cuda_stream
-            rt.check(rt.lib().spt_scene_render_async(lz.sc.handle, C.byref(lz.cam), col.data_ptr(),
-                                                     lz.seeds0.data_ptr(), sout.data_ptr(), px.data_ptr(), w, h, r0,
-                                                     r1, 0, SPP, mode, cnt.data_ptr(), st))
-            torch.cuda.synchronize()
-            gcol = col.cpu().numpy().reshape(-1, 3)
-            gpx = px.cpu().numpy().view(np.uint32).reshape(h, w)
-            gs = sout.cpu().numpy().view(np.uint32).reshape(-1, 2)
+            f = lz.frame.reset(colors=-7.25, pixels=0x25A5A5A5, seeds=0x5EADBEEF)
+            f.render(SPP, mode=mode, counted=True, rows=(r0, r1))
+            gcol, gs, gpx = f.host()
+            gcol, gs, gpx = gcol.reshape(-1, 3), gs.reshape(-1, 2), gpx.reshape(h, w)
             assert (gcol[ins].view(np.uint32) == ref[0].reshape(-1, 3)[ins].view(np.uint32)).all()
             assert (gcol[~ins] == np.float32(-7.25)).all()
             assert (gpx[r0:r1] == ref[2].reshape(h, w)[r0:r1]).all()
             assert (np.delete(gpx, np.s_[r0:r1], 0) == 0x25A5A5A5).all()
             assert (gs[ins] == ref[1].reshape(-1, 2)[ins]).all() and (gs[~ins] == 0x5EADBEEF).all()
-            assert cnt.tolist() == ref[3], (cnt.tolist(), ref[3])
+            assert tuple(f.counters.tolist()) == ref[3], (f.counters.tolist(), ref[3])
     finally:
         lz.close()

@@ -6,10 +6,10 @@ parking can go wrong: lanes past the frame's edge, both block shapes (the LDS
 area is carved per wave of a 4- or a 16-wave block), a row window,
 progressive launches that start from a stored colour, and both iteration
 forms (one and two ray queries per iteration)."""
-import ctypes as C
-
 import numpy as np
 import pytest
+
+import spt_check
 
 pytestmark = pytest.mark.gpu
 
@@ -21,38 +21,7 @@ SHAPES = ["wpb=4", "wpb=16"]        # small frames pick 16 on their own, the 108
 def refs(oracle):
     """Oracle frames, computed once per (w, h, passes) and handed out as
     read-only arrays: colours, seeds, pixels, counters."""
-    cache = {}
-
-    def get(w, h, steps):
-        key = (w, h, tuple(steps))
-        if key not in cache:
-            S, n = oracle.cornell()
-            cam = oracle.cornell_camera(w, h)
-            col = np.zeros(3 * w * h, np.float32)
-            seeds = oracle.seeds(w, h)
-            px = np.zeros(w * h, np.uint32)
-            cnt = [0, 0, 0, 0]
-            first = 0
-            for k in steps:
-                c = oracle.smallpt_render(S, n, cam, col, seeds, px, w, h, first, k)
-                cnt = [a + b for a, b in zip(cnt, c)]
-                first += k
-            for a in (col, seeds, px):
-                a.setflags(write=False)
-            cache[key] = (col, seeds, px, cnt)
-        return cache[key]
-
-    return get
-
-
-def _same(f, ref, counted):
-    col, seeds, px, cnt = ref
-    assert (f.colors.view(np.uint32) == col.view(np.uint32)).all(), "HDR not bit-exact (%d slots)" % (
-        (f.colors.view(np.uint32) != col.view(np.uint32)).sum())
-    assert (f.pixels == px).all()
-    assert (f.seeds == seeds).all()
-    if counted:
-        assert f.counters == cnt, (f.counters, cnt)
+    return spt_check.frame_cache(oracle)
 
 
 @pytest.mark.parametrize("counted", [False, True])
@@ -65,18 +34,16 @@ def test_ragged_tiles_both_block_shapes(rt, refs, monkeypatch, w, h, tune, count
     monkeypatch.setenv("RT_SPT_TUNE", tune)
     f = rt.SmallptFrame(w, h)
     f.render(3, counters=counted)
-    _same(f, refs(w, h, [3]), counted)
+    spt_check.assert_same(f, refs(w, h, [3]), counted=counted)
 
 
 @pytest.mark.parametrize("tune", SHAPES)
 def test_row_window_leaves_other_rows_untouched(rt, oracle, monkeypatch, tune):
     """64x40, rows [8, 29): the window's pixels equal the oracle's and every
     colour, pixel and seed slot outside it keeps the value it had."""
-    import torch
     monkeypatch.setenv("RT_SPT_TUNE", tune)
     w, h, r0, r1, spp = 64, 40, 8, 29, 3
-    S, n = rt.scenes.cornell()
-    cam = rt.scenes.cornell_camera(w, h)
+    S, n, cam = rt.scenes.smallpt("cornell", w, h)
     col0 = np.full(3 * w * h, -7.25, np.float32)
     px0 = np.full(w * h, 0xA5A5A5A5, np.uint32)
     seeds0 = rt.scenes.seeds(w, h)
@@ -92,19 +59,13 @@ def test_row_window_leaves_other_rows_untouched(rt, oracle, monkeypatch, tune):
     inside[h - r1:h - r0] = True
     want_seeds = np.where(np.repeat(inside.reshape(-1), 2), rseeds, sentinel)
 
-    dev = torch.device("cuda", 0)
-    col = torch.from_numpy(col0.copy()).to(dev)
-    px = torch.from_numpy(px0.view(np.int32).copy()).to(dev)
-    sin = torch.from_numpy(seeds0.view(np.int32).copy()).to(dev)
-    sout = torch.from_numpy(np.full(2 * w * h, sentinel, np.uint32).view(np.int32)).to(dev)
     sc = rt.SmallptScene(S, n)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    rt.check(rt.lib().spt_scene_render_async(sc.handle, C.byref(cam), col.data_ptr(), sin.data_ptr(), sout.data_ptr(),
-                                             px.data_ptr(), w, h, r0, r1, 0, spp, 0, None, st))
-    torch.cuda.synchronize()
-    assert (col.cpu().numpy().view(np.uint32) == rcol.view(np.uint32)).all()
-    assert (px.cpu().numpy().view(np.uint32) == rpx).all()
-    assert (sout.cpu().numpy().view(np.uint32) == want_seeds).all()
+    f = rt.SmallptDeviceFrame(sc, cam, w, h).reset(colors=-7.25, pixels=0xA5A5A5A5, seeds=sentinel)
+    f.render(spp, rows=(r0, r1))
+    col, sout, px = f.host()
+    assert (col.view(np.uint32) == rcol.view(np.uint32)).all()
+    assert (px == rpx).all()
+    assert (sout == want_seeds).all()
     sc.close()
 
 
@@ -123,8 +84,8 @@ def test_progressive_state_through_the_parked_colour(rt, refs, monkeypatch, tune
     b.render(5, counters=counted)
     assert (a.colors.view(np.uint32) == b.colors.view(np.uint32)).all()
     assert (a.pixels == b.pixels).all() and (a.seeds == b.seeds).all()
-    _same(a, refs(w, h, [2, 3]), counted)
-    _same(b, refs(w, h, [5]), counted)
+    spt_check.assert_same(a, refs(w, h, [2, 3]), counted=counted)
+    spt_check.assert_same(b, refs(w, h, [5]), counted=counted)
 
 
 @pytest.mark.parametrize("tune", SHAPES)
@@ -135,9 +96,9 @@ def test_single_sample_launches(rt, refs, monkeypatch, tune):
     w, h = 37, 21
     f = rt.SmallptFrame(w, h)
     f.render(1, counters=False)
-    _same(f, refs(w, h, [1]), False)
+    spt_check.assert_same(f, refs(w, h, [1]), counted=False)
     f.render(1, counters=False)
-    _same(f, refs(w, h, [1, 1]), False)
+    spt_check.assert_same(f, refs(w, h, [1, 1]), counted=False)
 
 
 @pytest.mark.parametrize("counted", [False, True])
@@ -151,4 +112,4 @@ def test_both_iteration_forms(rt, refs, monkeypatch, dual, tune, counted):
     w, h = 37, 21
     f = rt.SmallptFrame(w, h)
     f.render(3, counters=counted)
-    _same(f, refs(w, h, [3]), counted)
+    spt_check.assert_same(f, refs(w, h, [3]), counted=counted)

@@ -20,6 +20,7 @@ def child():
     import numpy as np
     import torch
     import rtamd
+    import _spt
     W, H = (int(v) for v in os.environ.get("WH", "1920x1080").split("x"))
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev)
@@ -35,53 +36,20 @@ def child():
             rtamd.check(L.rtw_render_async(d_prims.data_ptr(), n, px.data_ptr(), W, H, 20, H - 70, None,
                                            st.cuda_stream))
     else:
-        SPP = int(os.environ.get("SPP", "64"))
-        r0, r1 = 0, H
-        if os.environ.get("BAND"):
-            from rtamd import dist as rdist
-            k, N = (int(v) for v in os.environ["BAND"].split("/"))
-            r0, r1 = rdist.row_band(k, N, H)
-        if os.environ.get("SCENE") == "c4":        # BASELINE configs[4] (8-wide hierarchy kernel)
-            S, n, cam = rtamd.scenes.complex10k()
-            rtamd.scenes.update_camera(cam, W, H)
-        else:
-            S, n = rtamd.scenes.cornell()
-            cam = rtamd.scenes.cornell_camera(W, H)
-        sc = rtamd.SmallptScene(S, n)
-        seeds0 = torch.from_numpy(rtamd.scenes.seeds(W, H).view(np.int32)).to(dev)
-        seeds = torch.empty_like(seeds0)
-        col = torch.zeros(3 * W * H, dtype=torch.float32, device=dev)
-        px = torch.zeros(W * H, dtype=torch.int32, device=dev)
-        grp = os.environ.get("GROUP")              # k/N: the interleaved share of rank k of N
+        # SCENE=c4: BASELINE configs[4] (8-wide hierarchy kernel); BAND / GROUP=k/N: a row band / the
+        # interleaved share of rank k of N
+        sc, frame, kw = _spt.frame_from_env()
         # COUNT=full: all four counters (the counted kernel); COUNT=rays: calls and samples only
         cmode = os.environ.get("COUNT", "")
-        cnt = torch.zeros(4, dtype=torch.int64, device=dev)
-        cm = {"cptr": cnt.data_ptr() if cmode else None,
+        cm = {"counted": bool(cmode),
               "mode": rtamd.SPT_PATH_TRACING | (rtamd.SPT_COUNT_RAYS if cmode == "rays" else 0)}
         plain = os.environ.get("WARM_PLAIN")       # warm-up launches uncounted (they learn the tile order)
 
         def run(warm=False):
-            mode, cptr = (0, None) if (warm and plain) else (cm["mode"], cm["cptr"])
-            if grp:
-                k, N = (int(v) for v in grp.split("/"))
-                rtamd.check(L.spt_scene_render_groups_async(sc.handle, C.byref(cam), col.data_ptr(),
-                                                            seeds0.data_ptr(), seeds.data_ptr(), px.data_ptr(),
-                                                            W, H, k, N, 0, SPP, mode, cptr, st.cuda_stream))
-                return
-            rtamd.check(L.spt_scene_render_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                                 seeds.data_ptr(), px.data_ptr(), W, H, r0, r1, 0, SPP, mode,
-                                                 cptr, st.cuda_stream))
-    for _ in range(int(os.environ.get("WARM", "3" if os.environ.get("SCENE") == "c4" else "1"))):
-        run(warm=True)
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(int(os.environ.get("REPS", "5"))):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(st)
-        run()
-        b.record(st)
-        torch.cuda.synchronize()
-        ts.append(a.elapsed_time(b))
+            frame.render(stream=st, **kw, **({} if (warm and plain) else cm))
+    warm = int(os.environ.get("WARM", "3" if os.environ.get("SCENE") == "c4" else "1"))
+    _spt.event_ms(lambda: run(warm=True), warm, 0, st)
+    ts = _spt.event_ms(run, 0, int(os.environ.get("REPS", "5")), st)
     if os.environ.get("PROF"):      # block counters of a tools-only instrumented build
         names = ["iter", "shadow", "nearest", "diff", "spec", "refr", "light", "bounce", "done",
                  "wcall", "wstep", "wleaf", "wshade", "flush"]   # flush: ring entries popped / passes

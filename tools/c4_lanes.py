@@ -12,7 +12,6 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
-import torch  # noqa: E402
 import wave_trace as wt  # noqa: E402
 
 rtamd = wt.rtamd
@@ -20,19 +19,11 @@ rtamd = wt.rtamd
 
 def main():
     import ctypes as C
-    dev = torch.device("cuda", 0)
     L = rtamd.lib()
     L.spt_trace_set.argtypes = [C.c_void_p]
-    S, n, cam = rtamd.scenes.complex10k()
-    rtamd.scenes.update_camera(cam, wt.W, wt.H)
-    sc = rtamd.SmallptScene(S, n)
-    seeds0 = torch.from_numpy(rtamd.scenes.seeds(wt.W, wt.H).view(np.int32)).to(dev)
-    seeds = torch.empty_like(seeds0)
-    col = torch.zeros(3 * wt.W * wt.H, dtype=torch.float32, device=dev)
-    px = torch.zeros(wt.W * wt.H, dtype=torch.int32, device=dev)
-    st = torch.cuda.current_stream(dev)
+    sc, frame, _ = wt._spt.frame_from_env(kind="complex", wh="%dx%d" % (wt.W, wt.H))
     for rep in range(3):                                 # learn the order, then the measured frame
-        t, gx, gy = wt.run(L, sc, cam, seeds0, seeds, col, px, 0, wt.H, st)
+        t, gx, gy = wt.run(L, frame, 0, wt.H)
     t = t[t[:, 1] != 0]
     s, m = t[:, 4].astype(np.float64), t[:, 5].astype(np.float64)
     ok = m > 0

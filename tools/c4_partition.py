@@ -16,7 +16,6 @@ frame must equal the full-frame render bit for bit (checked).
     LIBS=a,b ROUNDS=2 QUICK=1 python tools/c4_partition.py   (A/B of build_ab/<lib> builds:
         one child process per lib and round; QUICK: balanced lists only)
 """
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -27,46 +26,34 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import rtamd  # noqa: E402
 from rtamd import dist as rdist  # noqa: E402
+import _spt  # noqa: E402
 
 W, H, SPP = 1920, 1080, int(os.environ.get("SPP", "64"))
 REPS = int(os.environ.get("REPS", "5"))
 dev = torch.device("cuda", 0)
-spheres, n, cam = rtamd.scenes.complex10k()
-rtamd.scenes.update_camera(cam, W, H)
-L = rtamd.lib()
+spheres, n, cam = rtamd.scenes.smallpt("complex", W, H)
 st = torch.cuda.current_stream(dev)
-seeds0 = torch.from_numpy(rtamd.scenes.seeds(W, H).view(np.int32)).to(dev)
 NG = rdist.group_count(W, H)
 
 
 def bufs():
-    return (torch.zeros(3 * W * H, dtype=torch.float32, device=dev), torch.empty_like(seeds0),
-            torch.zeros(W * H, dtype=torch.int32, device=dev))
+    """A zeroed device frame; its scene is set by the render that uses it."""
+    return rtamd.SmallptDeviceFrame(None, cam, W, H)
 
 
 def timed(fn):
-    ts = []
-    for _ in range(REPS):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(st)
-        fn()
-        b.record(st)
-        torch.cuda.synchronize()
-        ts.append(a.elapsed_time(b))
+    ts = _spt.event_ms(fn, 0, REPS, st)
     return float(np.median(ts)), min(ts)
 
 
-def render_list(sc, lst, col, sd, px, cost=None, flags=0):
-    rtamd.check(L.spt_scene_render_list_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                              sd.data_ptr(), px.data_ptr(), W, H, lst.data_ptr(), lst.numel(), 0,
-                                              SPP, flags, None, cost.data_ptr() if cost is not None else None,
-                                              st.cuda_stream))
+def render_list(sc, lst, f, cost=None, flags=0):
+    f.scene = sc
+    f.render(SPP, mode=flags, groups=lst, cost=cost, stream=st)
 
 
-def render_groups(sc, k, N, col, sd, px):
-    rtamd.check(L.spt_scene_render_groups_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                                sd.data_ptr(), px.data_ptr(), W, H, k, N, 0, SPP, 0, None,
-                                                st.cuda_stream))
+def render_groups(sc, k, N, f):
+    f.scene = sc
+    f.render(SPP, share=(k, N), stream=st)
 
 
 def main():
@@ -81,14 +68,10 @@ def main():
         return
     quick = os.environ.get("QUICK") == "1"
     sc_full = rtamd.SmallptScene(spheres, n)
-    ref = bufs()
+    ref, scratch = rtamd.SmallptDeviceFrame(sc_full, cam, W, H), bufs()
     for _ in range(3):
-        rtamd.check(L.spt_scene_render_async(sc_full.handle, C.byref(cam), ref[0].data_ptr(), seeds0.data_ptr(),
-                                             ref[1].data_ptr(), ref[2].data_ptr(), W, H, 0, H, 0, SPP, 0, None,
-                                             st.cuda_stream))
-    full_ms, _ = timed(lambda: rtamd.check(L.spt_scene_render_async(
-        sc_full.handle, C.byref(cam), ref[0].data_ptr(), seeds0.data_ptr(), ref[1].data_ptr(), ref[2].data_ptr(),
-        W, H, 0, H, 0, SPP, 0, None, st.cuda_stream)))
+        ref.render(SPP, stream=st)
+    full_ms, _ = timed(lambda: ref.render(SPP, stream=st))
     print("full frame (1 GPU): %.2f ms" % full_ms, flush=True)
     for N in [int(v) for v in os.environ.get("NS", "4,8").split(",")]:
         # interleaved (one scene per rank: each learns its own order)
@@ -97,26 +80,27 @@ def main():
         for k in (range(N) if not quick else []):
             sc = rtamd.SmallptScene(spheres, n)
             for _ in range(3):
-                render_groups(sc, k, N, *out)
-            res.append(timed(lambda: render_groups(sc, k, N, *out)))
+                render_groups(sc, k, N, out)
+            res.append(timed(lambda: render_groups(sc, k, N, out)))
             sc.close()
         if not quick:
             print("N=%d interleaved: per rank %s ms; max %.2f" % (N, [round(r[0], 2) for r in res],
                                                                    max(r[0] for r in res)), flush=True)
-            ok = torch.equal(out[0].view(torch.int32), ref[0].view(torch.int32)) and torch.equal(out[2], ref[2])
+            ok = torch.equal(out.colors.view(torch.int32), ref.colors.view(torch.int32)) and \
+                torch.equal(out.pixels, ref.pixels)
             print("  assembled == full frame: %s" % ok, flush=True)
         # learning frame: interleaved lists with per-group costs
         cost = torch.zeros(NG, dtype=torch.int32, device=dev)
         sc = rtamd.SmallptScene(spheres, n)
         lists0 = [torch.tensor(rdist.interleaved_groups(k, N, W, H), dtype=torch.int32, device=dev) for k in range(N)]
         for k in range(N):
-            render_list(sc, lists0[k], *bufs())                      # code objects, caches
+            render_list(sc, lists0[k], scratch)                      # code objects, caches
         cost.zero_()
         for k in range(N):
-            render_list(sc, lists0[k], *out, cost=cost)
+            render_list(sc, lists0[k], out, cost=cost)
         cmax = torch.zeros_like(cost)                            # each group's longest tile: the order key
         for k in range(N):
-            render_list(sc, lists0[k], *bufs(), cost=cmax, flags=rtamd.SPT_COST_MAX)
+            render_list(sc, lists0[k], scratch, cost=cmax, flags=rtamd.SPT_COST_MAX)
         torch.cuda.synchronize()
         c = cost.cpu().numpy().astype(np.int64)
         parts = rdist.balanced_partition(c, N, order_key=None if os.environ.get("C4_SUM_ORDER") else
@@ -143,12 +127,11 @@ def main():
             for k in range(N):
                 lst = torch.tensor(parts[k], dtype=torch.int32, device=dev)
                 for _ in range(2):
-                    render_list(sc, lst, *out)
-                res.append(timed(lambda: render_list(sc, lst, *out)))
+                    render_list(sc, lst, out)
+                res.append(timed(lambda: render_list(sc, lst, out)))
             print("N=%d balanced [%s]: per rank %s ms; max %.2f (min-of-reps max %.2f)" % (
                 N, pol, [round(r[0], 2) for r in res], max(r[0] for r in res), max(r[1] for r in res)), flush=True)
-            ok = torch.equal(out[0].view(torch.int32), ref[0].view(torch.int32)) and torch.equal(out[2], ref[2]) \
-                and torch.equal(out[1], ref[1])
+            ok = out.same_bits(ref)
             print("  assembled == full frame: %s" % ok, flush=True)
         if tune0 is None:
             os.environ.pop("RT_SPT_TUNE", None)

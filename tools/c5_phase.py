@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "se-195-project-ray-tracer_amd"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import rtamd  # noqa: E402
+import _spt  # noqa: E402
 
 W, H, SPP = 1920, 1080, int(os.environ.get("SPP", "64"))
 N = int(os.environ.get("N", "1"))
@@ -29,13 +30,7 @@ def main():
     L = rtamd.lib()
     L.spt_trace_set.argtypes = [C.c_void_p]
     L.spt_trace_only_group.argtypes = [C.c_int]
-    S, n, cam = rtamd.scenes.complex10k()
-    rtamd.scenes.update_camera(cam, W, H)
-    sc = rtamd.SmallptScene(S, n)
-    seeds0 = torch.from_numpy(rtamd.scenes.seeds(W, H).view(np.int32)).to(dev)
-    seeds = torch.empty_like(seeds0)
-    col = torch.zeros(3 * W * H, dtype=torch.float32, device=dev)
-    px = torch.zeros(W * H, dtype=torch.int32, device=dev)
+    sc, frame, _ = _spt.frame_from_env(kind="complex", wh="%dx%d" % (W, H))
     st = torch.cuda.current_stream(dev)
     nw = (((W + 7) // 8) * ((H + 7) // 8) + 64) * 8    # work items (upper bound: tiles split up to 8 ways)
     buf = torch.zeros(nw * 16, dtype=torch.int32, device=dev)
@@ -43,18 +38,12 @@ def main():
     K = [0]
 
     def launch():
-        rtamd.check(L.spt_scene_render_groups_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                                    seeds.data_ptr(), px.data_ptr(), W, H, K[0], N, 0, SPP, 0, None,
-                                                    st.cuda_stream))
+        frame.render(SPP, share=(K[0], N), stream=st)
 
     def traced(tag):
         buf.zero_()
         rtamd.check(L.spt_trace_set(C.c_void_p(buf.data_ptr())))
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(st)
-        launch()
-        b.record(st)
-        torch.cuda.synchronize()
+        ms, = _spt.event_ms(launch, 0, 1, st)
         rtamd.check(L.spt_trace_set(None))
         t = buf.cpu().numpy().view(np.uint32).reshape(nw, 16).astype(np.int64)
         t = t[t[:, 1] != 0]
@@ -64,7 +53,7 @@ def main():
         walk, leaf, trips, lruns, queries = t[:, 8], t[:, 9], t[:, 10], t[:, 11], t[:, 12]
         live = it_sum > 0
         print("== %s: kernel %.2f ms (HIP events), %d waves with work, span %.2f ms" % (
-            tag, a.elapsed_time(b), live.sum(), (t1[live].max() - t0[live].min()) * 1e-5))
+            tag, ms, live.sum(), (t1[live].max() - t0[live].min()) * 1e-5))
         ghz = tot[live] / np.maximum(dur[live], 1e-9) * 1e-6
         print("   s_memtime rate: %.2f GHz median (cycles / wall)" % np.median(ghz))
         idx = np.argsort(-dur * live)[:8]

@@ -9,47 +9,20 @@ sys.path.insert(0, os.path.join(ROOT, "se-195-project-ray-tracer_amd"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import rtamd  # noqa: E402
+import _spt  # noqa: E402
 
-W, H = 1920, 1080
-SPP = int(os.environ.get("SPP", "1"))
-dev = torch.device("cuda", 0)
-spheres, n, cam = rtamd.scenes.complex10k()
-rtamd.scenes.update_camera(cam, W, H)
-sc = rtamd.SmallptScene(spheres, n)
-seeds0 = torch.from_numpy(rtamd.scenes.seeds(W, H).view(np.int32)).to(dev)
-seeds = torch.empty_like(seeds0)
-col = torch.zeros(3 * W * H, dtype=torch.float32, device=dev)
-px = torch.zeros(W * H, dtype=torch.int32, device=dev)
-cnt = torch.zeros(20, dtype=torch.int64, device=dev)   # [4..7]: RT_BVH_STATS builds
-st = torch.cuda.current_stream(dev)
+# BAND=k/N: row band k of N (per-GPU work at N GPUs); GROUP=k/N: interleaved 8-row groups of rank k of N
+sc, frame, kw = _spt.frame_from_env(kind="complex", wh="1920x1080", spp=1)
+W, H, SPP, n = frame.w, frame.h, kw["nsamples"], sc.n
+R0, R1 = kw.get("rows", (0, H))
+cnt = torch.zeros(20, dtype=torch.int64, device=frame.device)   # [4..7]: RT_BVH_STATS builds
+st = torch.cuda.current_stream(frame.device)
 L = rtamd.lib()
-
-
-R0, R1 = 0, H
-if os.environ.get("BAND"):                          # BAND=k/N: row band k of N (per-GPU work at N GPUs)
-    from rtamd import dist as rdist
-    k, N = (int(v) for v in os.environ["BAND"].split("/"))
-    R0, R1 = rdist.row_band(k, N, H)
-
-
-GROUP = os.environ.get("GROUP")                    # GROUP=k/N: interleaved 8-row groups of rank k of N
-
-
 MODE = rtamd.SPT_COUNT_RAYS if os.environ.get("COUNTED") == "rays" else 0
 
 
 def run(c=None):
-    cp = c.data_ptr() if c is not None else None
-    mode = MODE if c is not None else 0
-    if GROUP:
-        k, N = (int(v) for v in GROUP.split("/"))
-        rtamd.check(L.spt_scene_render_groups_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                                    seeds.data_ptr(), px.data_ptr(), W, H, k, N, 0, SPP, mode, cp,
-                                                    st.cuda_stream))
-    else:
-        rtamd.check(L.spt_scene_render_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                             seeds.data_ptr(), px.data_ptr(), W, H, R0, R1, 0, SPP, mode, cp,
-                                             st.cuda_stream))
+    frame.render(mode=MODE if c is not None else 0, counted=c if c is not None else False, stream=st, **kw)
 
 
 stats = getattr(L, "spt_bvh_stats_read", None)   # RT_BVH_STATS builds only
@@ -73,17 +46,10 @@ if stats:
           "%.1f nodes each, %d >= 512" % (bs[15], bs[16] / max(bs[15], 1), bs[20], bs[17], bs[18] / max(bs[17], 1), bs[19]))
     print("  node visits in the first 64 / 256 / 1024 nodes of the ray's octant layout: %.3f %.3f %.3f" % (
         bs[21] / max(bs[0], 1), bs[22] / max(bs[0], 1), bs[23] / max(bs[0], 1)))
-ts = []
 COUNTED = os.environ.get("COUNTED") in ("1", "rays")   # time the counted kernel (full, or rays-only) instead
 for _ in range(int(os.environ.get("WARM", "0"))):      # uncounted frames first (they teach the tile order)
     run(None)
-for _ in range(int(os.environ.get("REPS", "1"))):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(st)
-    run(cnt if COUNTED else None)
-    b.record(st)
-    torch.cuda.synchronize()
-    ts.append(a.elapsed_time(b))
+ts = _spt.event_ms(lambda: run(cnt if COUNTED else None), 0, int(os.environ.get("REPS", "1")), st)
 ms = float(np.median(ts))
 print("c5 %dx%d rows [%d,%d) spp=%d spheres=%d%s%s: %.2f ms (median of %d, min %.2f), rays %d, %.1f Mrays/s, sphere tests %d" % (
     W, H, R0, R1, SPP, n, " counted" if COUNTED else "", " (rays only)" if MODE else "", ms, len(ts), min(ts), rays, rays / ms / 1e3, int(cnt[2])))

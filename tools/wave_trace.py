@@ -16,20 +16,19 @@ sys.path.insert(0, os.path.join(ROOT, "se-195-project-ray-tracer_amd"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import rtamd  # noqa: E402
+import _spt  # noqa: E402
 from rtamd import dist as rdist  # noqa: E402
 
 W, H, SPP = 1920, 1080, int(os.environ.get("SPP", "64"))
 
 
-def run(L, sc, cam, seeds0, seeds, col, px, r0, r1, st):
+def run(L, frame, r0, r1):
     ntiles = ((W + 7) // 8) * ((r1 - r0 + 7) // 8)
     gx, gy = (ntiles + 15) // 16, 16           # blocks (upper bound), waves per block
     nw = gx * gy
-    buf = torch.zeros(nw * 16, dtype=torch.int32, device=seeds.device)
+    buf = torch.zeros(nw * 16, dtype=torch.int32, device=frame.device)
     rtamd.check(L.spt_trace_set(C.c_void_p(buf.data_ptr())))
-    rtamd.check(L.spt_scene_render_async(sc.handle, C.byref(cam), col.data_ptr(), seeds0.data_ptr(),
-                                         seeds.data_ptr(), px.data_ptr(), W, H, r0, r1, 0, SPP, 0, None,
-                                         st.cuda_stream))
+    frame.render(SPP, rows=(r0, r1))
     torch.cuda.synchronize()
     rtamd.check(L.spt_trace_set(None))
     t = buf.cpu().numpy().view(np.uint32).reshape(nw, 16).astype(np.int64)
@@ -83,25 +82,13 @@ def main():
     save = None
     if "--save" in sys.argv:
         save = sys.argv[sys.argv.index("--save") + 1]
-    dev = torch.device("cuda", 0)
     L = rtamd.lib()
     L.spt_trace_set.argtypes = [C.c_void_p]
-    if os.environ.get("SCENE") == "c4":            # BASELINE configs[4] (hierarchy kernel)
-        S, n, cam = rtamd.scenes.complex10k()
-        rtamd.scenes.update_camera(cam, W, H)
-    else:
-        S, n = rtamd.scenes.cornell()
-        cam = rtamd.scenes.cornell_camera(W, H)
-    sc = rtamd.SmallptScene(S, n)
-    seeds0 = torch.from_numpy(rtamd.scenes.seeds(W, H).view(np.int32)).to(dev)
-    seeds = torch.empty_like(seeds0)
-    col = torch.zeros(3 * W * H, dtype=torch.float32, device=dev)
-    px = torch.zeros(W * H, dtype=torch.int32, device=dev)
-    st = torch.cuda.current_stream(dev)
-    run(L, sc, cam, seeds0, seeds, col, px, 0, H, st)          # warm-up
+    sc, frame, _ = _spt.frame_from_env(wh="%dx%d" % (W, H))        # SCENE=c4: BASELINE configs[4] (hierarchy kernel)
+    run(L, frame, 0, H)                                            # warm-up
     for N in [int(v) for v in os.environ.get("NS", "1,2,4,8").split(",")]:
         r0, r1 = rdist.row_band(0 if N == 1 else N // 2, N, H)
-        t, gx, gy = run(L, sc, cam, seeds0, seeds, col, px, r0, r1, st)
+        t, gx, gy = run(L, frame, r0, r1)
         analyse("N%d" % N, t, gx, gy, save)
 
 
