@@ -195,7 +195,9 @@ int spt_scene_destroy(spt_scene *scene);
  *   [0] kernel family: SPT_GEO_LDS (the scene staged in LDS, full scan),
  *       SPT_GEO_GLOBAL (full scan from global memory), SPT_GEO_BVH (binary
  *       hierarchy walked from global memory), SPT_GEO_WIDE (8-wide hierarchy
- *       in LDS)
+ *       in LDS).  (An SPT_GEO_LDS scene's launch runs the global-memory
+ *       kernel where its block -- scene copy and per-wave areas, [16] -- would
+ *       exceed a compute unit's LDS: the same bits either way.)
  *   [1] spheres   [2] lights (emitters)
  *   [3] spheres tested outside the hierarchy (radius > 64 x the median, <= 16)
  *   [4] binary hierarchy nodes   [5] 8-wide nodes   [6] 8-wide levels

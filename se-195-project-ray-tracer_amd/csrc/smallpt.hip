@@ -27,11 +27,12 @@
 #include "rt_common.h"
 #include "rt_glibc_math.h"
 #include "spt_policy.h"
+#include "spt_layout.h"
 
 namespace rt {
 namespace smallpt {
 
-constexpr int MAX_LDS_BYTES = 96 * 1024; // per-block scene copy: 48 B per sphere + 48 B per light
+using namespace sptlayout;               // the kernel families, variant predicates and LDS layout
 constexpr float EPS = 0.01f;             // geom.h:29
 constexpr float PI_F = 3.14159265358979323846f;
 constexpr int DIFF = 0, SPEC = 1;   // REFR = 2 is the remaining case
@@ -305,35 +306,11 @@ __device__ __forceinline__ int to_int(float x)
     const float c = (x < 0.f) ? 0.f : ((x > 1.f) ? 1.f : x);
     return (int)(rtm::powf(c, 1.f / 2.2f) * 255.f + .5f);
 }
-
-// Occupancy of the kernel variants (__launch_bounds__ minimum waves per
-// SIMD; every bound measured against its neighbours):
-//   full-scan one-query kernels: unbounded (1);
-//   the uncounted two-query kernel (DUAL): 7 -- 85 -> 72 VGPRs, no VGPR
-//     spills, occupancy 5 -> 7: Cornell 1080p 17.87 -> 17.3 ms.  8 measured
-//     without scratch (colour, coordinates and camera terms parked: 64
-//     VGPRs, private segment 0) and not kept: 8 waves cap the kernel at 80
-//     SGPRs, the rest go through v_readlane in every iteration (+1.05 % VALU
-//     instructions), and the eighth wave buys no rate: 16.98 ms against
-//     16.57 ms for the same code at 7 (profiles/r07).  With
-//     its shadow rays deferred to the per-wave ring (DQ) it holds 70 VGPRs
-//     (71 reading the spheres from global memory);
-//   binary-hierarchy (GEO_BVH) kernels: 6 -- 93 -> 80 VGPRs (2 spilled): the
-//     latency-bound walk gains more from the sixth wave than the spills cost;
-//   8-wide (GEO_WIDE) kernels: 4 -- 126 VGPRs unbounded; 5 or 6 spill;
-//   counted hierarchy kernels (not timed): 4, room for the counters.
-constexpr int SPT_MINWAVES = 1, SPT_DUAL_MINWAVES = 7, BVH_MINWAVES = 6, WIDE_MINWAVES = 4, BVH_MINWAVES_COUNT = 4;
-constexpr int GEO_LDS = 0, GEO_GLOBAL = 1, GEO_BVH = 2, GEO_WIDE = 3;
-constexpr int GS_BYTES = 6160;      // GEO_BVH group staging strip: 8 x 96 colour floats, 8 x 64 seed words, 8 x 32 pixels, count
-constexpr int PARK_SLOTS = 3;       // full-scan kernels' parked per-lane state: the running-average colour
-constexpr int PARK_BYTES_PER_WAVE = PARK_SLOTS * 64 * 4;
-constexpr int PARK_HEAD_BYTES = 64;  //   and, before the waves' areas, the block's copy of the camera terms
-// The uncounted two-query kernel (DQ below): per wave nine lane-private slots --
-// the colour, the parked previous sample's radiance, the second pending
-// contribution -- then the shadow-ray ring, seven dwords per entry as SoA.
-constexpr int DQ_SLOTS = 9;
-constexpr int DQ_DW_PER_WAVE = DQ_SLOTS * 64 + 7 * sptpolicy::SQ_RING;
-constexpr int DQ_BYTES_PER_WAVE = 4 * DQ_DW_PER_WAVE;
+// A pixel, smallptCPU.cpp:120-122.
+__device__ __forceinline__ uint32_t pack_rgb(float r, float g, float b)
+{
+    return (uint32_t)(to_int(r) | (to_int(g) << 8) | (to_int(b) << 16));
+}
 
 // DUAL (path tracing, full-scan geometry, scenes with exactly one light): a
 // DIFF vertex builds its light sample's shadow ray AND its bounce ray in the
@@ -353,9 +330,7 @@ constexpr int DQ_BYTES_PER_WAVE = 4 * DQ_DW_PER_WAVE;
 // carries (8 or 4), or 0 -- no cooperative code (windows without a
 // cooperative tier: the full frame, N = 2 shares).
 template <bool DL, bool COUNT, int GEO, bool DUAL = false, bool RAYS = false, int CG = 0>
-__global__ void __launch_bounds__(1024, GEO == 2 ? ((COUNT || RAYS) ? BVH_MINWAVES_COUNT : BVH_MINWAVES)
-                                              : GEO == 3 ? ((COUNT || RAYS) ? BVH_MINWAVES_COUNT : WIDE_MINWAVES)
-                                              : ((DUAL && !COUNT && !RAYS) ? SPT_DUAL_MINWAVES : SPT_MINWAVES))
+__global__ void __launch_bounds__(1024, variant_of(GEO, DL, DUAL, COUNT, RAYS, CG).min_waves())
 render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam,
               float *__restrict__ colors, const uint32_t *seeds_in,
               uint32_t *seeds_out, uint32_t *__restrict__ pixels, int w, int h,
@@ -366,20 +341,22 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
               BvhView bvh, unsigned long long *__restrict__ counters, int *__restrict__ work, int split,
               int nheavy, int sflags)
 {
-    constexpr bool LDS = GEO == GEO_LDS;
+    // The variant (spt_layout.h): its predicates here are the ones launch()
+    // sizes the dynamic LDS by, and every LDS offset below is that header's.
+    constexpr Variant V = variant_of(GEO, DL, DUAL, COUNT, RAYS, CG);
+    constexpr bool LDS = V.lds();
     // GEO_WIDE: persistent waves -- each wave takes 8x8 tiles from a work
     // counter (in the adaptive order's slot sequence, heaviest groups first)
     // until the window is done, so a block's LDS copy of the hierarchy is
     // made once and a CU never idles behind one block's slowest wave.
-    constexpr bool PERSIST = GEO == GEO_WIDE;
+    constexpr bool PERSIST = V.persist();
     // PARK (full-scan kernels): state that is touched once per sample or
     // once per pass B, not in the sphere loop, lives in LDS after the scene
-    // copy instead of in registers.  The running-average colour sits in a
-    // lane-private area (per wave PARK_SLOTS x 64 dwords, dword slot * 64 +
-    // lane: every access is conflict-free; only the lane itself ever reads or
-    // writes its dwords, so no barrier is needed); the camera terms sit
-    // once per block before it.  Arithmetic, draws and stores are unchanged.
-    constexpr bool PARK = GEO == GEO_LDS || GEO == GEO_GLOBAL;
+    // copy instead of in registers.  The running-average colour sits in the
+    // wave's lane-private slots (only the lane itself ever reads or writes
+    // its dwords, so no barrier is needed); the camera terms sit once per
+    // block before them.  Arithmetic, draws and stores are unchanged.
+    constexpr bool PARK = V.park();
     // DQ (the uncounted two-query kernels): the shadow rays are deferred.  A
     // lit DIFF vertex pushes its shadow ray (origin, direction, maxt) into a
     // wave-private FIFO ring in LDS and keeps the contribution c = thr * (e *
@@ -403,15 +380,13 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
     //   * when no lane has a sample left: the drain that ends the wave's loop.
     // Every lane of the wave stays in the loop until then (a lane out of
     // samples, or past the frame's edge, idles but still pops entries).
-    constexpr bool DQ = DUAL && !COUNT && !RAYS && PARK;
-    constexpr int WAVE_DW = DQ ? DQ_DW_PER_WAVE : PARK_SLOTS * 64;
-    constexpr int SQ_RING = sptpolicy::SQ_RING;
-    // Dynamic LDS carve (16-B multiples): geo | emi | col (n each) | lrec (3 per light),
-    // a copy of the scene's global SoA (spt_scene_create); PARK: then the
-    // parking area, PARK_HEAD_BYTES and PARK_BYTES_PER_WAVE (DQ:
-    // DQ_BYTES_PER_WAVE) per wave of the block.
+    constexpr bool DQ = V.dq();
+    constexpr int WAVE_DW = wave_dwords(DQ);
+    constexpr int SQ_RING = RING_FIELD_DW;
+    // Dynamic LDS (spt_layout.h): LDS: the scene copy; PARK: then the parking
+    // area -- its head, and WAVE_DW dwords per wave of the block.
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int park_off = (PARK && LDS) ? 16 * (3 * nspheres + 3 * (nlights > 0 ? nlights : 1)) : 0;
+    const int park_off = park_offset(V, nspheres, nlights);
     // (the thread index is re-read behind an empty asm at every use: hoisted
     // out of the loop, the address would be carried in a register of its own)
     const auto park_ptr = [&]() {
@@ -423,7 +398,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
     const auto ring_ptr = [&]() {
         int t = (int)threadIdx.x;
         asm volatile("" : "+v"(t));
-        return (float *)(smem + park_off + PARK_HEAD_BYTES) + (t >> 6) * WAVE_DW + DQ_SLOTS * 64;
+        return (float *)(smem + park_off + PARK_HEAD_BYTES) + (t >> 6) * WAVE_DW + RING_BASE_DW;
     };
     // The camera terms of pass B (twelve floats, with 1 / w and 1 / h) head
     // the parking area: read there by every lane at one address (broadcast)
@@ -439,7 +414,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
     Scene S;
     if (LDS) {
         float4 *s = (float4 *)smem;
-        const int nrec = 3 * nspheres + 3 * (nlights > 0 ? nlights : 1);   // a light-free scene: one zero record
+        const int nrec = scene_records(nspheres, nlights);
         for (int i = threadIdx.x; i < nrec; i += blockDim.x) s[i] = g_geo[i];
         __syncthreads();
         S.geo = s; S.emi = s + nspheres; S.col = s + 2 * nspheres; S.lrec = s + 3 * nspheres;
@@ -449,8 +424,8 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
     S.nlights = nlights;
     S.n = nspheres;
     const DynGeo geo{S.geo, S.n};
-    // GEO_WIDE LDS carve: the wide nodes (7 x 16 B each), then per wave of the
-    // block its lanes' stacks ((wdepth - 1) entries x 64 lanes x 4 B).
+    // GEO_WIDE (spt_layout.h): the wide nodes, then per wave of the block its
+    // lanes' stacks.
     const uint4 *wL = (const uint4 *)smem;
     unsigned *wstk = nullptr;
     if (GEO == GEO_WIDE) {
@@ -458,8 +433,8 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
         for (int i = threadIdx.x; i < 7 * bvh.wnodes; i += blockDim.x) d[i] = bvh.wnode[i];
         if (COUNT)
             for (int i = threadIdx.x; i < 2 * bvh.wnodes; i += blockDim.x) d[7 * bvh.wnodes + i] = bvh.wmax[i];
-        wstk = (unsigned *)(smem + (size_t)(COUNT ? 144 : 112) * bvh.wnodes) +
-               (size_t)(threadIdx.x >> 6) * 64 * (bvh.wdepth - 1);
+        wstk = (unsigned *)(smem + wide_stack_offset(bvh.wnodes, COUNT)) +
+               (size_t)(threadIdx.x >> 6) * WIDE_LEVEL_DW * (bvh.wdepth - 1);
         __syncthreads();
     }
 
@@ -475,7 +450,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
     // Compiled into the hierarchy kernels only: in the full-scan kernels
     // (Cornell) the order/cost plumbing cost 1.4 % of the frame and 8 % of an
     // N = 8 band (measured A/B) although it is never used there.
-    constexpr bool SCHED = GEO == GEO_BVH || GEO == GEO_WIDE;
+    constexpr bool SCHED = V.sched();
     constexpr bool CALLS = COUNT || RAYS;           // the call / sample counters are kept
     Counts cnt = {0, 0, 0, 0};
     SPT_PROF_ONLY(unsigned prof_l[PB_N] = {}, prof_w[PB_N] = {};)
@@ -557,10 +532,10 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
     // GSTORE (hierarchy kernels): per group of the block a 32x8 staging
     // strip in LDS -- colours, seeds, pixels -- and an arrival count.
     // (Addresses recomputed where used: held across the loop they spilled.)
-    constexpr bool GSTORE = GEO == GEO_BVH;
+    constexpr bool GSTORE = V.gstore();
 #define GS_BASE() (smem + (size_t)((threadIdx.x >> 6) >> 2) * GS_BYTES)
     if (GSTORE) {
-        if ((threadIdx.x & 255) == 0) *(int *)(GS_BASE() + 6144) = 0;
+        if ((threadIdx.x & 255) == 0) *(int *)(GS_BASE() + GS_COUNT_OFF) = 0;
         __syncthreads();
     }
     int x = (tile % tiles_x) * 8 + (li & 7);
@@ -599,9 +574,9 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
         }
         if (PARK && first_sample > 0) {         // (first_sample == 0: the first sample overwrites it)
             float *p = park_ptr();
-            p[0] = col.x;
-            p[64] = col.y;
-            p[128] = col.z;
+            p[64 * SLOT_COL] = col.x;
+            p[64 * (SLOT_COL + 1)] = col.y;
+            p[64 * (SLOT_COL + 2)] = col.z;
         }
         const float invW = 1.f / w, invH = 1.f / h;             // :80-81
         // Refill state: the lane's pixel is px_ok (its group pgrp, started at
@@ -652,29 +627,29 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
         SPT_PROF_ONLY(for (int b = 0; b < 3; b++) walk.pf_l[b] = walk.pf_w[b] = 0;)
         bool walking = false;  //   and whether it is suspended mid-walk
         // DQ: the lane's pending contributions, oldest first (npend of them:
-        // pc0 in registers, the second in LDS slots 6..8; their ring positions
+        // pc0 in registers, the second in the SLOT_PEND slots; their ring positions
         // in pidx's bytes 0 and 1), of which the oldest npark belong to the
-        // parked previous sample (LDS slots 3..5); and the wave's ring, q_count
+        // parked previous sample (the SLOT_RAD slots); and the wave's ring, q_count
         // entries from q_head (wave-uniform), flushed at q_T.
         v3 pc0 = mk(0.f, 0.f, 0.f);
         int pidx = 0, npend = 0, npark = 0;
         int q_head = 0, q_count = 0;
         const int q_T = sptpolicy::sq_threshold(sptpolicy::sflags_sq(sflags));
-        // DQ: sample number `current`'s radiance r into the parked running
-        // average (:110-118, the arithmetic of the PARK form below)
+        // PARK: sample number `current`'s radiance r into the parked running
+        // average (:110-118, the arithmetic of the register form below)
         const auto fold = [&](const v3 r, const int current) {
             float *p = park_ptr();
             v3 c = r;
             if (current != 0) {
                 const float k1 = (float)current;
                 const float k2 = rcp_nr(k1 + 1.f);
-                c.x = (p[0] * k1 + r.x) * k2;
-                c.y = (p[64] * k1 + r.y) * k2;
-                c.z = (p[128] * k1 + r.z) * k2;
+                c.x = (p[64 * SLOT_COL] * k1 + r.x) * k2;
+                c.y = (p[64 * (SLOT_COL + 1)] * k1 + r.y) * k2;
+                c.z = (p[64 * (SLOT_COL + 2)] * k1 + r.z) * k2;
             }
-            p[0] = c.x;
-            p[64] = c.y;
-            p[128] = c.z;
+            p[64 * SLOT_COL] = c.x;
+            p[64 * (SLOT_COL + 1)] = c.y;
+            p[64 * (SLOT_COL + 2)] = c.z;
         };
         constexpr float nc = 1.f, nt = 1.5f;
         // prio_sched: the three level boundaries as fractions of the samples
@@ -696,8 +671,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                             colors[3 * (size_t)i] = col.x;
                             colors[3 * (size_t)i + 1] = col.y;
                             colors[3 * (size_t)i + 2] = col.z;
-                            pixels[(size_t)y * w + x] =
-                                (uint32_t)(to_int(col.x) | (to_int(col.y) << 8) | (to_int(col.z) << 16));
+                            pixels[(size_t)y * w + x] = pack_rgb(col.x, col.y, col.z);
                         }
                         seeds_out[2 * (size_t)i] = s0;
                         seeds_out[2 * (size_t)i + 1] = s1;
@@ -873,12 +847,14 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                         if (npark > 0) {
                             float *p = park_ptr();
                             if (lit) {
-                                p[192] = p[192] + pc0.x;
-                                p[256] = p[256] + pc0.y;
-                                p[320] = p[320] + pc0.z;
+                                p[64 * SLOT_RAD] = p[64 * SLOT_RAD] + pc0.x;
+                                p[64 * (SLOT_RAD + 1)] = p[64 * (SLOT_RAD + 1)] + pc0.y;
+                                p[64 * (SLOT_RAD + 2)] = p[64 * (SLOT_RAD + 2)] + pc0.z;
                             }
                             npark--;
-                            if (npark == 0) fold(mk(p[192], p[256], p[320]), first_sample + k - 1);
+                            if (npark == 0)
+                                fold(mk(p[64 * SLOT_RAD], p[64 * (SLOT_RAD + 1)], p[64 * (SLOT_RAD + 2)]),
+                                     first_sample + k - 1);
                         } else if (lit) {
                             rad = vadd(rad, pc0);
                         }
@@ -886,7 +862,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                         pidx >>= 8;
                         if (npend > 0) {
                             const float *p = park_ptr();
-                            pc0 = mk(p[384], p[448], p[512]);
+                            pc0 = mk(p[64 * SLOT_PEND], p[64 * (SLOT_PEND + 1)], p[64 * (SLOT_PEND + 2)]);
                         }
                     }
                     q_head = __builtin_amdgcn_readfirstlane(sptpolicy::sq_wrap(q_head + m));
@@ -1112,9 +1088,9 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                                 pidx = pos;
                             } else {
                                 float *p = park_ptr();
-                                p[384] = c.x;
-                                p[448] = c.y;
-                                p[512] = c.z;
+                                p[64 * SLOT_PEND] = c.x;
+                                p[64 * (SLOT_PEND + 1)] = c.y;
+                                p[64 * (SLOT_PEND + 2)] = c.z;
                                 pidx |= pos << 8;
                             }
                             npend++;
@@ -1199,27 +1175,15 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                     // them (the previous sample is folded by now: f_ends)
                     if (npend > 0) {
                         float *p = park_ptr();
-                        p[192] = rad.x;
-                        p[256] = rad.y;
-                        p[320] = rad.z;
+                        p[64 * SLOT_RAD] = rad.x;
+                        p[64 * (SLOT_RAD + 1)] = rad.y;
+                        p[64 * (SLOT_RAD + 2)] = rad.z;
                         npark = npend;
                     } else {
                         fold(rad, current);
                     }
                 } else if constexpr (PARK) {
-                    // the same average on the parked colour: loaded, updated and written back here
-                    float *p = park_ptr();
-                    v3 c = rad;
-                    if (current != 0) {
-                        const float k1 = (float)current;
-                        const float k2 = rcp_nr(k1 + 1.f);
-                        c.x = (p[0] * k1 + rad.x) * k2;
-                        c.y = (p[64] * k1 + rad.y) * k2;
-                        c.z = (p[128] * k1 + rad.z) * k2;
-                    }
-                    p[0] = c.x;
-                    p[64] = c.y;
-                    p[128] = c.z;
+                    fold(rad, current);         // the parked colour: loaded, updated and written back
                 } else if (current == 0) {
                     col = rad;
                 } else {
@@ -1246,27 +1210,26 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
         }
         if (GSTORE) {                                   // staged: the group's last wave stores it
             float *gs_col = (float *)GS_BASE();
-            uint32_t *gs_seed = (uint32_t *)(GS_BASE() + 3072), *gs_px = (uint32_t *)(GS_BASE() + 5120);
+            uint32_t *gs_seed = (uint32_t *)(GS_BASE() + GS_SEED_OFF), *gs_px = (uint32_t *)(GS_BASE() + GS_PX_OFF);
             const int c = (wave & 3) * 8 + (lane & 7), r = lane >> 3;
             if (nsamples > 0) {
                 gs_col[r * 96 + 3 * c] = col.x;
                 gs_col[r * 96 + 3 * c + 1] = col.y;
                 gs_col[r * 96 + 3 * c + 2] = col.z;
-                gs_px[r * 32 + c] = (uint32_t)(to_int(col.x) | (to_int(col.y) << 8) | (to_int(col.z) << 16));
+                gs_px[r * 32 + c] = pack_rgb(col.x, col.y, col.z);
             }
             gs_seed[r * 64 + 2 * c] = s0;
             gs_seed[r * 64 + 2 * c + 1] = s1;
         } else if (lead && !refill && (!DQ || active)) {   // (refill: stored as each pixel finished)
             if (PARK && nsamples > 0) {          // the parked colour back
                 const float *p = park_ptr();
-                col = mk(p[0], p[64], p[128]);
+                col = mk(p[64 * SLOT_COL], p[64 * (SLOT_COL + 1)], p[64 * (SLOT_COL + 2)]);
             }
             if (nsamples > 0) {
                 colors[3 * (size_t)i] = col.x;
                 colors[3 * (size_t)i + 1] = col.y;
                 colors[3 * (size_t)i + 2] = col.z;
-                pixels[(size_t)y * w + x] =
-                    (uint32_t)(to_int(col.x) | (to_int(col.y) << 8) | (to_int(col.z) << 16));
+                pixels[(size_t)y * w + x] = pack_rgb(col.x, col.y, col.z);
             }
             seeds_out[2 * (size_t)i] = s0;
             seeds_out[2 * (size_t)i + 1] = s1;
@@ -1290,10 +1253,11 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
         // the neighbouring tiles' and reach HBM as partial lines when the
         // neighbours finish much later: 71 MB written per frame for 50 MB.)
         const float *gs_col = (const float *)GS_BASE();
-        const uint32_t *gs_seed = (const uint32_t *)(GS_BASE() + 3072), *gs_px = (const uint32_t *)(GS_BASE() + 5120);
+        const uint32_t *gs_seed = (const uint32_t *)(GS_BASE() + GS_SEED_OFF);
+        const uint32_t *gs_px = (const uint32_t *)(GS_BASE() + GS_PX_OFF);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         int old = 0;
-        if (lane == 0) old = atomicAdd((int *)(GS_BASE() + 6144), 1);
+        if (lane == 0) old = atomicAdd((int *)(GS_BASE() + GS_COUNT_OFF), 1);
         old = __shfl(old, 0, 64);
         if (old == 3) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -1474,7 +1438,7 @@ struct spt_scene {
 };
 
 namespace {
-using sptbvh::wide_lds_bytes;
+using namespace sptlayout;
 
 // One render call, as the entry points receive it: rows [r0, r1) (every
 // gstride-th 8-row group), or (list) the caller's nlist tile groups over the
@@ -1492,9 +1456,7 @@ struct RenderCall {
     unsigned *cost = nullptr;
 };
 
-// Counter modes of a launch: none, all four counters, or calls and samples
-// only (SPT_COUNT_RAYS: the uncounted queries).
-enum { CNT_NONE = 0, CNT_FULL = 1, CNT_RAYS = 2 };
+// The counter mode of a call (spt_layout.h: none, all four, calls and samples).
 int counter_mode(const RenderCall &c)
 {
     return !c.counters ? CNT_NONE : (c.mode & SPT_COUNT_RAYS) ? CNT_RAYS : CNT_FULL;
@@ -1504,48 +1466,11 @@ int counter_mode(const RenderCall &c)
 // per-block LDS copy if the scene fits, else global memory.
 int scene_geo(const spt_scene &sc)
 {
-    using namespace rt::smallpt;
     static_assert(GEO_LDS == SPT_GEO_LDS && GEO_GLOBAL == SPT_GEO_GLOBAL && GEO_BVH == SPT_GEO_BVH &&
                   GEO_WIDE == SPT_GEO_WIDE, "rt_hip.h's family codes (spt_scene_info)");
     if (sc.bvh.wnode) return GEO_WIDE;
     if (sc.bvh.node) return GEO_BVH;
-    const size_t bytes = (size_t)(3 * sc.n + 3 * std::max(sc.nlights, 1)) * sizeof(float4);
-    return (bytes <= (size_t)MAX_LDS_BYTES && !sc.force_global) ? GEO_LDS : GEO_GLOBAL;
-}
-
-// The render_kernel instantiation for a launch: every one has the same
-// signature, so the runtime choices become template arguments here and
-// nowhere else.
-using Kernel = decltype(&rt::smallpt::render_kernel<false, false, 0>);
-
-template <bool DL, bool COUNT, int GEO, bool DUAL, bool RAYS>
-Kernel pick_cg(int cg)
-{
-    Kernel kern = rt::smallpt::render_kernel<DL, COUNT, GEO, DUAL, RAYS, 0>;
-    if constexpr (GEO == rt::smallpt::GEO_WIDE) {
-        if (cg == 8) kern = rt::smallpt::render_kernel<DL, COUNT, GEO, DUAL, RAYS, 8>;
-        else if (cg == 4) kern = rt::smallpt::render_kernel<DL, COUNT, GEO, DUAL, RAYS, 4>;
-        else if (cg == 2) kern = rt::smallpt::render_kernel<DL, COUNT, GEO, DUAL, RAYS, 2>;
-    }
-    return kern;
-}
-
-template <int GEO, bool DL, bool DUAL>
-Kernel pick_counted(int cmode, int cg)
-{
-    if (cmode == CNT_FULL) return pick_cg<DL, true, GEO, DUAL, false>(cg);
-    if (cmode == CNT_RAYS) return pick_cg<DL, false, GEO, DUAL, true>(cg);
-    return pick_cg<DL, false, GEO, DUAL, false>(cg);
-}
-
-template <int GEO>
-Kernel pick_mode(bool dl, int cmode, bool dual, int cg)
-{
-    if (dl) return pick_counted<GEO, true, false>(cmode, cg);
-    if constexpr (GEO != rt::smallpt::GEO_BVH && GEO != rt::smallpt::GEO_WIDE) {
-        if (dual) return pick_counted<GEO, false, true>(cmode, cg);
-    }
-    return pick_counted<GEO, false, false>(cmode, cg);
+    return (scene_bytes(sc.n, sc.nlights) <= MAX_LDS_BYTES && !sc.force_global) ? GEO_LDS : GEO_GLOBAL;
 }
 
 // Whether a launch runs the two-query iteration (one_light: the scene has
@@ -1561,56 +1486,88 @@ bool two_query_form(int geo, bool dl, bool one_light)
     // (The hierarchy walks keep the one-query form: their two resumable
     // walks in one loop spill)
     const int dual_env = getenv("RT_SPT_DUAL") ? atoi(getenv("RT_SPT_DUAL")) : -1;
-    using namespace rt::smallpt;
     return one_light && dual_env != 0 && !dl && (geo == GEO_LDS || geo == GEO_GLOBAL);
 }
 
-// dual: two_query_form's answer; cg: lanes per pixel of the launch's
-// cooperative tier (8-wide kernels; 0: none -- the kernel carries the
-// cooperative walk only when the launch has such a tier, and only the group
-// size it uses).
-Kernel pick_kernel(int geo, bool dl, int cmode, bool dual, int cg)
+// The variant of a launch of call c in blocks of wpb waves: the scene's
+// family (the LDS family only while the block fits a CU's LDS: launch_geo),
+// the estimator, the counter mode, two_query_form's answer, and cg, the lanes
+// per pixel of the launch's cooperative tier (8-wide kernels; 0: none -- the
+// kernel carries the cooperative walk only when the launch has such a tier,
+// and only the group size it uses).
+Variant launch_variant(const spt_scene &sc, const RenderCall &c, const SceneSizes &sizes, int wpb, int cg)
 {
-    using namespace rt::smallpt;
-    if (geo == GEO_WIDE) return pick_mode<GEO_WIDE>(dl, cmode, dual, cg);
-    if (geo == GEO_BVH) return pick_mode<GEO_BVH>(dl, cmode, dual, cg);
-    if (geo == GEO_LDS) return pick_mode<GEO_LDS>(dl, cmode, dual, cg);
-    return pick_mode<GEO_GLOBAL>(dl, cmode, dual, cg);
+    const bool dl = (c.mode & ~(SPT_COUNT_RAYS | SPT_COST_MAX)) == SPT_DIRECT_LIGHTING;
+    Variant v{scene_geo(sc), dl, false, counter_mode(c), cg};
+    v.dual = two_query_form(v.geo, dl, sc.nlights == 1);
+    v.geo = launch_geo(v, sizes, wpb);
+    return v;
 }
 
-// Launches render_kernel for call c in shape g: the LDS size, the work
-// counters of a persistent launch and the packed words of spt_policy.h.
+// The render_kernel instantiation of a variant: every one has the same
+// signature, so the variant's fields become template arguments here and
+// nowhere else.
+using Kernel = decltype(&rt::smallpt::render_kernel<false, false, 0>);
+
+template <bool DL, bool COUNT, int GEO, bool DUAL, bool RAYS>
+Kernel pick_cg(const Variant &v)
+{
+    Kernel kern = rt::smallpt::render_kernel<DL, COUNT, GEO, DUAL, RAYS, 0>;
+    if constexpr (GEO == GEO_WIDE) {
+        if (v.cg == 8) kern = rt::smallpt::render_kernel<DL, COUNT, GEO, DUAL, RAYS, 8>;
+        else if (v.cg == 4) kern = rt::smallpt::render_kernel<DL, COUNT, GEO, DUAL, RAYS, 4>;
+        else if (v.cg == 2) kern = rt::smallpt::render_kernel<DL, COUNT, GEO, DUAL, RAYS, 2>;
+    }
+    return kern;
+}
+
+template <int GEO, bool DL, bool DUAL>
+Kernel pick_counted(const Variant &v)
+{
+    if (v.count()) return pick_cg<DL, true, GEO, DUAL, false>(v);
+    if (v.rays()) return pick_cg<DL, false, GEO, DUAL, true>(v);
+    return pick_cg<DL, false, GEO, DUAL, false>(v);
+}
+
+template <int GEO>
+Kernel pick_mode(const Variant &v)
+{
+    if (v.dl) return pick_counted<GEO, true, false>(v);
+    if constexpr (GEO != GEO_BVH && GEO != GEO_WIDE) {
+        if (v.dual) return pick_counted<GEO, false, true>(v);
+    }
+    return pick_counted<GEO, false, false>(v);
+}
+
+Kernel pick_kernel(const Variant &v)
+{
+    if (v.geo == GEO_WIDE) return pick_mode<GEO_WIDE>(v);
+    if (v.geo == GEO_BVH) return pick_mode<GEO_BVH>(v);
+    if (v.geo == GEO_LDS) return pick_mode<GEO_LDS>(v);
+    return pick_mode<GEO_GLOBAL>(v);
+}
+
+// Launches render_kernel for call c in shape g: the variant and its LDS size
+// (spt_layout.h), the work counters of a persistent launch and the packed
+// words of spt_policy.h.
 int launch(const spt_scene &sc, const RenderCall &c, const Shape &g)
 {
-    using namespace rt::smallpt;
-    const int geo = scene_geo(sc), cmode = counter_mode(c), n = sc.n;
-    const bool dl = (c.mode & ~(SPT_COUNT_RAYS | SPT_COST_MAX)) == SPT_DIRECT_LIGHTING;
+    const int n = sc.n;
     const float4 *gg = sc.d_soa, *ge = gg + n, *gc = ge + n, *gl = gc + n;
-    size_t lds = geo == GEO_LDS ? (size_t)(3 * n + 3 * std::max(sc.nlights, 1)) * sizeof(float4) : 0;
-    if (geo == GEO_BVH) lds = (size_t)(g.wpb / 4) * GS_BYTES;
-    // full-scan kernels: the parked per-lane state, after the scene copy (the
-    // 16-wave shape's reservation below covers it unless the scene is large)
-    // (the uncounted two-query kernel: with its pending slots and shadow-ray ring)
-    const bool dual = two_query_form(geo, dl, sc.nlights == 1);
-    const bool dq = dual && cmode == CNT_NONE;
-    if (geo == GEO_LDS || geo == GEO_GLOBAL)
-        lds += PARK_HEAD_BYTES + (size_t)g.wpb * (dq ? DQ_BYTES_PER_WAVE : PARK_BYTES_PER_WAVE);
-    if (g.wpb == 16 && lds < 81 * 1024) lds = 81 * 1024;   // > half the CU's 160 KiB: one block per CU
-    int *work = nullptr;
-    if (geo == GEO_WIDE) {
-        lds = wide_lds_bytes(sc.bvh.wnodes, sc.bvh.wdepth, g.wpb, cmode == CNT_FULL);
-        if (!(work = sptsched::work_entry(sc.work, c.stream)))
-            return rtrt::check_launch("spt work counters") ? RT_ERR_HIP : RT_ERR_INVALID;
-    }
     const sptpolicy::Tiers t = sptpolicy::heavy_tiers(g, sc.cus);
-    const Kernel kern = pick_kernel(geo, dl, cmode, dual, t.cg);
-    sc.last = {sc.last.count + 1, g.wpb, g.nblocks, t.cg, t.n1, t.n2, dual ? 1 : 0, (int)lds};
-    hipLaunchKernelGGL(kern, dim3(g.nblocks), dim3(64 * g.wpb), lds, c.stream, sc.d_spheres, n, *c.cam, c.colors,
-                       c.seeds_in, c.seeds_out, c.pixels, c.w, c.h, c.r0, c.r1, g.tiles_x, g.ntiles, g.nslots,
+    const SceneSizes sizes{n, sc.nlights, sc.bvh.wnodes, sc.bvh.wdepth};
+    const Variant v = launch_variant(sc, c, sizes, g.wpb, t.cg);
+    const size_t lds = block_lds_bytes(v, sizes, g.wpb);
+    int *work = nullptr;
+    if (v.persist() && !(work = sptsched::work_entry(sc.work, c.stream)))
+        return rtrt::check_launch("spt work counters") ? RT_ERR_HIP : RT_ERR_INVALID;
+    sc.last = {sc.last.count + 1, g.wpb, g.nblocks, t.cg, t.n1, t.n2, v.dual ? 1 : 0, (int)lds};
+    hipLaunchKernelGGL(pick_kernel(v), dim3(g.nblocks), dim3(64 * g.wpb), lds, c.stream, sc.d_spheres, n, *c.cam,
+                       c.colors, c.seeds_in, c.seeds_out, c.pixels, c.w, c.h, c.r0, c.r1, g.tiles_x, g.ntiles, g.nslots,
                        g.gstride, c.first_sample, c.nsamples, sptpolicy::prio_schedule(g), g.order, g.cost, gg, ge, gc,
-                       gl, sc.nlights, sc.bvh, c.counters, work, geo == GEO_WIDE ? sptpolicy::split_word(g, t) : 0,
+                       gl, sc.nlights, sc.bvh, c.counters, work, v.persist() ? sptpolicy::split_word(g, t) : 0,
                        sptpolicy::pack_nheavy(t.n1, t.n2),
-                       sptpolicy::pack_sflags(sc.no_refr, g.cost_max, dq ? sptpolicy::sq_threshold(g.tune.sq) : 0));
+                       sptpolicy::pack_sflags(sc.no_refr, g.cost_max, v.dq() ? sptpolicy::sq_threshold(g.tune.sq) : 0));
     return RT_OK;
 }
 

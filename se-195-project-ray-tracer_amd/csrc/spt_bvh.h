@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <vector>
 #include "../../include/rt_hip.h"
+#include "spt_layout.h"
 
 namespace sptbvh {
 
@@ -385,13 +386,14 @@ struct WideBuild {
 
 // ---------------------------------------------------------------------------
 // The wide layout a scene gets.  A block of wpb waves stages the nodes in LDS
-// (112 B each, plus 32 B of per-slot highest indices for the counted any-hit
-// walk) and keeps one 256-B stack level per wave and level below the root;
-// the budget leaves a CU's 160 KiB room for that one block.
-constexpr size_t WIDE_LDS_MAX = 144 * 1024;
+// (with the per-slot highest indices of the counted any-hit walk: a tree is
+// chosen by its counted form) and keeps its waves' stacks behind them; the
+// sizes and the budget, which leaves a CU room for that one block, are
+// spt_layout.h's.
+constexpr size_t WIDE_LDS_MAX = sptlayout::WIDE_LDS_MAX;
 inline size_t wide_lds_bytes(int wnodes, int wdepth, int wpb, bool counted = true)
 {
-    return (size_t)(counted ? 144 : 112) * wnodes + (size_t)wpb * 256 * (wdepth > 1 ? wdepth - 1 : 1);
+    return sptlayout::wide_lds_bytes(wnodes, wdepth, wpb, counted);
 }
 
 // Builds into wb the 8-wide tree of b with the smallest leaf size in {8, 12,

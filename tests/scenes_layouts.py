@@ -72,6 +72,15 @@ def cloud(n, seed=1):
     return pack(cloud_rows(n, seed))
 
 
+def cloud_one_light(n, seed=1):
+    """cloud(n) with emitter 1 as its only light: spheres 2 and 3 emit
+    nothing and are grey (single-light scenes run the two-query kernels)."""
+    rows = cloud_rows(n, seed)
+    rows[2:4, 4:7] = 0.0
+    rows[2:4, 7:10] = 0.5
+    return pack(rows)
+
+
 # Sizes of cloud(n) for the three layout classes past leaf 8 (cloud(3000)):
 # each sits clear of its class's boundaries -- 0.9 n and 1.1 n land in the
 # same class (test_bvh_layouts.py checks all three, and the summary of the

@@ -3,7 +3,8 @@ its own (tests/scenes_layouts.py): 8-wide trees with leaves of 12 and 16
 spheres, the binary walk a scene falls back to when no 8-wide tree fits, the
 cooperative walks (eight, four and two lanes per pixel) on scenes with SPEC
 and REFR spheres, several lights and direct lighting, the edges of the
-always / tree partition, and frames smaller than one block.
+always / tree partition, frames smaller than one block, and the dynamic LDS
+each kernel family's launch asks for (csrc/spt_layout.h, restated here).
 
 The reference is always the oracle's full scan (oracle.smallpt_render, the
 restatement of Intersect / IntersectP), computed once per (scene, frame,
@@ -296,3 +297,101 @@ def test_tiny_frame_row_window(rt, world, monkeypatch, name, env, family):
             assert tuple(f.counters.tolist()) == ref[3], (f.counters.tolist(), ref[3])
     finally:
         lz.close()
+
+
+# ---- LDS bytes per family ---------------------------------------------------
+# The figures of DESIGN.md §3's table, restated: 16 B per scene record, a 64-B
+# head, 768 B per wave (the parked colour) or 5,440 B (with the deferred shadow
+# rays' slots and ring), a 6,160-B strip per tile group, and at least 81 KiB
+# for a 16-wave block.
+SMALL = (40, 24)        # 15 tiles: one 16-wave block, four 4-wave ones
+RESERVED = 81 * 1024
+
+
+def _full_scan_bytes(records, wpb, deferred):
+    b = 16 * records + 64 + wpb * (5440 if deferred else 768)
+    return max(b, RESERVED) if wpb == 16 else b
+
+
+@pytest.mark.parametrize("geo", [None, "global"])
+@pytest.mark.parametrize("counted", [False, True])
+@pytest.mark.parametrize("wpb", [4, 16])
+def test_lds_bytes_of_the_full_scan_kernels(rt, world, monkeypatch, wpb, counted, geo):
+    """Cornell (9 spheres, one light: 30 records), path tracing: the bytes
+    each launch asks for, in both block shapes, uncounted (the two-query
+    kernel with deferred shadow rays) and counted, with the scene copied into
+    LDS and (RT_SPT_GEO=global) read from global memory -- no copy then."""
+    monkeypatch.setenv("RT_SPT_TUNE", "wpb=%d" % wpb)
+    monkeypatch.delenv("RT_SPT_GEO", raising=False)
+    if geo:
+        monkeypatch.setenv("RT_SPT_GEO", geo)
+    w, h = SMALL
+    lz = _open(rt, world, "cornell", w, h)
+    try:
+        assert lz.sc.info()["family"] == ("GEO_GLOBAL" if geo else "GEO_LDS")
+        got = lz.render(0, counted)
+        info = lz.sc.info()
+        assert info["wpb"] == wpb and info["two_query"], info
+        want = _full_scan_bytes(0 if geo else 30, wpb, not counted)
+        if not geo:
+            assert want == {(4, False): 22304, (16, False): 87584, (4, True): 480 + 64 + 4 * 768,
+                            (16, True): 82944}[(wpb, counted)]
+        assert info["lds_bytes"] == want, info
+        spt_check.assert_same(got, world[1]("cornell", w, h, 0))
+    finally:
+        lz.close()
+
+
+@pytest.mark.parametrize("wpb", [4, 16])
+def test_lds_bytes_of_the_binary_walk(rt, world, monkeypatch, wpb):
+    """The smallest hierarchy scene with RT_SPT_WIDE=0: one staging strip per
+    tile group of the block, (wpb / 4) * 6160 B -- and for the 16-wave block
+    the reservation that keeps it alone on its CU, as for every 16-wave block
+    but the 8-wide kernels'."""
+    monkeypatch.setenv("RT_SPT_WIDE", "0")
+    monkeypatch.setenv("RT_SPT_TUNE", "wpb=%d" % wpb)
+    w, h = SMALL
+    lz = _open(rt, world, "n256", w, h)
+    try:
+        assert lz.sc.info()["family"] == "GEO_BVH"
+        got = lz.render(0, False)
+        info = lz.sc.info()
+        assert info["wpb"] == wpb, info
+        strips = (wpb // 4) * 6160
+        assert info["lds_bytes"] == (strips if wpb == 4 else max(strips, RESERVED)), info
+        spt_check.assert_same(got, world[1]("n256", w, h, 0))
+    finally:
+        lz.close()
+
+
+@pytest.mark.parametrize("n,kept", [(1500, True), (1700, False)])
+def test_lds_family_only_while_its_block_fits_a_cu(rt, monkeypatch, n, kept):
+    """A one-light cloud scanned in full (RT_SPT_NO_BVH), uncounted, in the
+    16-wave block shape: sixteen waves' rings take 87,104 B, so the scene copy
+    fits beside them up to 1,597 spheres.  1,500 spheres launch the LDS family;
+    1,700 -- still the LDS family by the scene's size -- launch the global-
+    memory kernel of the same variant, inside a CU's 160 KiB.  Either way the
+    frame equals the one RT_SPT_GEO=global renders, bit for bit."""
+    monkeypatch.setenv("RT_SPT_NO_BVH", "1")
+    monkeypatch.setenv("RT_SPT_TUNE", "wpb=16")
+    w, h = SMALL
+    S, ns = sl.cloud_one_light(n)
+    frames = []
+    for geo in (None, "global"):
+        monkeypatch.delenv("RT_SPT_GEO", raising=False)
+        if geo:
+            monkeypatch.setenv("RT_SPT_GEO", geo)
+        lz = Launcher(rt, S, ns, sl.cloud_camera(w, h), w, h)
+        try:
+            info = lz.sc.info()
+            assert info["family"] == ("GEO_GLOBAL" if geo else "GEO_LDS") and info["nlights"] == 1, info
+            assert info["nodes"] == 0
+            frames.append(lz.render(0, False))
+            info = lz.sc.info()
+            assert info["family"] == ("GEO_GLOBAL" if geo else "GEO_LDS")       # the scene's family, whatever ran
+            assert info["wpb"] == 16 and info["two_query"], info
+            assert info["lds_bytes"] <= 163840, info
+            assert info["lds_bytes"] == _full_scan_bytes(3 * n + 3 if kept and not geo else 0, 16, True), info
+        finally:
+            lz.close()
+    spt_check.assert_same(frames[0], frames[1])       # colours, seeds, pixels
