@@ -387,17 +387,29 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
     // area -- its head, and WAVE_DW dwords per wave of the block.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int park_off = park_offset(V, nspheres, nlights);
-    // (the thread index is re-read behind an empty asm at every use: hoisted
-    // out of the loop, the address would be carried in a register of its own)
+    // The lane's parking address -- head, wave x WAVE_DW, lane -- and its
+    // wave's ring base do not change during a launch.  HELD variants state
+    // them as plain expressions of the thread index: the compiler computes
+    // them once per wave, before the pixel loop, and keeps the lane's address
+    // in a register for the whole launch, the ring base derived from it (at
+    // occupancy 7 the two-query kernel has that register: 70 -> 71 of 72
+    // VGPRs).  Rebuilt at every use they cost six VALU instructions a time in
+    // blocks that run with few lanes active.  (Stated this way, not through
+    // a variable of their own, the hierarchy kernels -- which have no parked
+    // state -- compile to the instructions they had; a wave-uniform ring base
+    // in a scalar register cost nine more scalar spills.)
+    // Not HELD (spt_layout.h names the variants that have no register to
+    // spare): the thread index is re-read behind an empty asm at every use,
+    // which keeps the address from being hoisted out of the loop.
+    constexpr bool HELD = V.held_addr();
     const auto park_ptr = [&]() {
         int t = (int)threadIdx.x;
-        asm volatile("" : "+v"(t));
+        if constexpr (!HELD) asm volatile("" : "+v"(t));
         return (float *)(smem + park_off + PARK_HEAD_BYTES) + (t >> 6) * WAVE_DW + (t & 63);
     };
-    // DQ: the wave's ring, field f of entry e at [f * SQ_RING + e]
+    // DQ (always HELD): the wave's ring, field f of entry e at [f * SQ_RING + e]
     const auto ring_ptr = [&]() {
-        int t = (int)threadIdx.x;
-        asm volatile("" : "+v"(t));
+        const int t = (int)threadIdx.x;
         return (float *)(smem + park_off + PARK_HEAD_BYTES) + (t >> 6) * WAVE_DW + RING_BASE_DW;
     };
     // The camera terms of pass B (twelve floats, with 1 / w and 1 / h) head
@@ -839,7 +851,8 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                     const unsigned long long unocc = __builtin_amdgcn_ballot_w64(have && !occ);
                     // owners, oldest entry first (:154-161, then :229-230).  (The
                     // fold stands inside the loop: hoisted behind it, to run once a
-                    // pass, it cost 13 more scalar spills and 2.3 % of the frame.)
+                    // pass, it cost 13 more scalar spills and 2.3 % of the frame;
+                    // tried again with the lane's address held: 14 more, 2.9 %.)
                     while (npend > 0) {
                         const int rel = sptpolicy::sq_rel(pidx & 255, q_head);
                         if (rel >= m) break;

@@ -30,8 +30,9 @@ enum { CNT_NONE = 0, CNT_FULL = 1, CNT_RAYS = 2 };
 //     SGPRs, the rest go through v_readlane in every iteration (+1.05 % VALU
 //     instructions), and the eighth wave buys no rate: 16.98 ms against
 //     16.57 ms for the same code at 7 (profiles/r07).  With
-//     its shadow rays deferred to the per-wave ring (dq) it holds 70 VGPRs
-//     (71 reading the spheres from global memory);
+//     its shadow rays deferred to the per-wave ring (dq) and the lane's
+//     parking address held across the loop it holds 71 VGPRs (72 reading
+//     the spheres from global memory);
 //   binary-hierarchy (GEO_BVH) kernels: 6 -- 93 -> 80 VGPRs (2 spilled): the
 //     latency-bound walk gains more from the sixth wave than the spills cost;
 //   8-wide (GEO_WIDE) kernels: 4 -- 126 VGPRs unbounded; 5 or 6 spill;
@@ -50,6 +51,11 @@ struct Variant {
     SPT_HD constexpr bool lds() const { return geo == GEO_LDS; }                   // the scene is copied into LDS
     SPT_HD constexpr bool park() const { return geo == GEO_LDS || geo == GEO_GLOBAL; }   // full scan: cold state parked in LDS
     SPT_HD constexpr bool dq() const { return dual && cmode == CNT_NONE && park(); }    // shadow rays deferred to the ring
+    // the lane's parking address is held in a register across the pixel loop
+    // (else: rebuilt from the thread index at every use -- the counted
+    // one-query global-memory kernels, which the register would take from 80
+    // VGPRs to 81 and from six waves per SIMD to five)
+    SPT_HD constexpr bool held_addr() const { return park() && !(geo == GEO_GLOBAL && cmode == CNT_FULL && !dual); }
     SPT_HD constexpr bool persist() const { return geo == GEO_WIDE; }              // waves fetch tiles from a work counter
     SPT_HD constexpr bool sched() const { return geo == GEO_BVH || geo == GEO_WIDE; }   // group order / cost code
     SPT_HD constexpr bool gstore() const { return geo == GEO_BVH; }                // stores staged per tile group
