@@ -239,6 +239,58 @@ int spt_scene_render_async(const spt_scene *scene, const rt_camera *camera, floa
  * launch). */
 int spt_scene_release_captures(const spt_scene *scene);
 
+/* Replaces spheres [first, first + count) of a prepared scene with
+ * spheres[0 .. count) (host memory) in place; the sphere count stays.  Any
+ * field may change.  The caller may change or free `spheres` as soon as the
+ * call returns (it is copied into page-locked staging the scene keeps).
+ * Device work is ordered on `stream` and nothing is synchronised: launches on
+ * `stream` enqueued before the call render the old scene, launches enqueued
+ * after it the new one.  (Launches on other streams need the caller's own
+ * ordering, as for any buffer.)  The scene's device must be the current one;
+ * update and render one scene from one host thread at a time.
+ *
+ * The host re-derives the light list, the light count and the no-refraction
+ * flag by spt_scene_create's rules, so kernel selection follows the edited
+ * scene.  A hierarchy scene is refitted on the device: the tree keeps its
+ * topology -- the always / tree partition, the leaf size, the octant child
+ * order, the 8-wide slots, the highest-index table and the escape links -- and
+ * every box, margin and quantised child box is recomputed from the new
+ * spheres with the builders' own expressions.  Culling is exact, so the frames
+ * are those of a scene created from the edited array, bit for bit; the learnt
+ * dispatch order and the work counters stay.  A tree refitted after large
+ * changes, or many times, may walk slower than a fresh one (its splits and
+ * its partition were chosen for the original spheres): spt_scene_create is the
+ * remedy.
+ *
+ * The first update of a scene builds what a refit needs (the topology, once
+ * more on the host; device metadata; staging) and is as slow as a create; a
+ * scene that is never updated pays nothing.  One path synchronises: when the
+ * edit raises the number of emitters above what the scene's light records
+ * have room for, the records are reallocated (stream and device are waited
+ * for; spt_scene_update_info counts it).  Graphs captured from this scene's
+ * launches before such a reallocation hold the old address: capture again.
+ *
+ * RT_ERR_INVALID, with the scene untouched: a null pointer, a range out of
+ * bounds, a capturing stream, another current device. */
+int spt_scene_update_async(spt_scene *scene, const rt_sphere *spheres, unsigned first, unsigned count,
+                           void *stream);
+/* Host bookkeeping of spt_scene_update_async, fills out[0 .. min(nout,
+ * SPT_UPDATE_INFO_WORDS)): [0] updates so far  [1] hierarchy refits run
+ * [2] light-record rebuilds  [3] synchronising reallocations  [4] bytes of
+ * refit metadata on the device (topology, entry boxes, node boxes; 0 before
+ * the first update and for a scene without a hierarchy). */
+#define SPT_UPDATE_INFO_WORDS 5
+int spt_scene_update_info(const spt_scene *scene, uint64_t *out, int nout);
+/* Blocking (waits for the device), for tests and tools: the hierarchy as the
+ * device holds it, five sections back to back in `out` -- the node records of
+ * the eight octant layouts (two float4 each), the entries' geometry (float4:
+ * centre, rad^2; tree entries, then the always entries), their sphere
+ * indices, the 8-wide nodes (28 words each), the 8-wide highest-index table
+ * (8 words per node) -- with their byte sizes in sizes[0..4] (all 0 for a
+ * scene without a hierarchy).  out == NULL: the sizes only; a `cap` below
+ * their sum fails RT_ERR_INVALID. */
+int spt_scene_read_hierarchy(const spt_scene *scene, void *out, size_t cap, size_t sizes[5]);
+
 /* spt_scene_render_async over an interleaved window: every pixel row y with
  * (y / 8) % ngroups == group, i.e. 8-row groups group, group + ngroups, ...
  * (0 <= group < ngroups).  The ngroups windows of a frame partition it; a
@@ -315,6 +367,9 @@ int spt_multi_create(const rt_sphere *spheres, unsigned nspheres, int w, int h, 
 int spt_multi_destroy(spt_multi *m);
 /* Re-uploads the scene to every band's device (ReInitSceneGPU). */
 int spt_multi_set_scene(spt_multi *m, const rt_sphere *spheres, unsigned nspheres);
+/* spt_scene_update_async on every band's scene, each on its band's stream:
+ * no band is re-prepared or waited for (but for the cases that call names). */
+int spt_multi_update_scene(spt_multi *m, const rt_sphere *spheres, unsigned first, unsigned count);
 /* Pixel-row bounds: rows[k] .. rows[k+1] hold band k's rows in FLIPPED
  * order, i.e. band k renders pixel rows [h - rows[k+1], h - rows[k]).
  * rows: ngpus + 1 ints. */

@@ -46,6 +46,7 @@ namespace {
 spt_multi *frame = nullptr;
 std::vector<int> devices;
 uint32_t *h_seeds = nullptr;
+unsigned frameSphereCount = 0;         // the sphere count the bands' scenes hold
 
 void die(const char *what, int rc)
 {
@@ -115,6 +116,7 @@ void AllocateBuffers()
     for (int i = 0; i < pixelCount; ++i) pixels[i] = i;
     int rc = spt_multi_create(spheres, sphereCount, width, height, devices.data(), (int)devices.size(), &frame);
     if (rc) die("Failed to create HIP buffers", rc);
+    frameSphereCount = sphereCount;
     rc = spt_multi_upload(frame, nullptr, h_seeds);
     if (rc) die("Failed to write the HIP seeds buffer", rc);
 }
@@ -196,11 +198,20 @@ void UpdateRenderingGPU()
             currentSample, sampleSec / 1000.f);
 }
 
-// ReInitSceneGPU (smallptGPU.cpp:784-803)
+// ReInitSceneGPU (smallptGPU.cpp:784-803).  The viewer calls it after moving
+// one sphere: with the sphere count unchanged the bands' scenes are updated in
+// place (no band waits, a hierarchy is refitted and its learnt order kept);
+// a changed count prepares them anew.  The same frames either way.
 void ReInitSceneGPU()
 {
     currentSample = 0;
-    int rc = spt_multi_set_scene(frame, spheres, sphereCount);
+    int rc;
+    if (sphereCount == frameSphereCount) {
+        rc = spt_multi_update_scene(frame, spheres, 0, sphereCount);
+    } else {
+        rc = spt_multi_set_scene(frame, spheres, sphereCount);
+        if (rc == 0) frameSphereCount = sphereCount;
+    }
     if (rc) die("Failed to write the HIP scene buffer", rc);
 }
 

@@ -1422,10 +1422,42 @@ __global__ void __launch_bounds__(256) list_dedup_kernel(const int *__restrict__
 #include <string>
 #include <vector>
 #include "rt_runtime.h"
+#include <memory>
 #include "spt_bvh.h"
+#include "spt_refit.h"
 #include "spt_sched.h"
 
 using sptpolicy::Shape;
+
+// What spt_scene_update_async keeps with a scene, built at the first update (a
+// scene that is never updated has none): the frozen topology of the hierarchy
+// on the host and on the device (sptrefit::Meta), the refit kernels' scratch,
+// the light indices, and two page-locked staging slots, so that the caller's
+// array is free when the call returns and no update waits for the one before it.
+struct SceneRefit {
+    static constexpr int SLOTS = 2;
+    sptrefit::Meta meta;
+    int *d_meta = nullptr;             // range | pos | order | wslot
+    float *d_scratch = nullptr;        // entry boxes (six planes of nb floats, padded to 16 B), then two float4 per node
+    int *d_lights = nullptr;           // light indices, ascending (n ints)
+    char *h_stage[SLOTS] = {};         // the changed spheres, then (at 44 n) the light indices
+    hipEvent_t done[SLOTS] = {};       // recorded behind the copies out of a slot
+    bool used[SLOTS] = {};
+    int next = 0;
+    int light_cap = 1;                 // light records d_soa has room for
+    bool boxes_valid = false;          // the entry boxes hold the whole scene (after the first refit)
+    uint64_t updates = 0, refits = 0, light_rebuilds = 0, reallocs = 0, meta_bytes = 0;
+    ~SceneRefit()
+    {
+        if (d_meta) (void)hipFree(d_meta);
+        if (d_scratch) (void)hipFree(d_scratch);
+        if (d_lights) (void)hipFree(d_lights);
+        for (int k = 0; k < SLOTS; k++) {
+            if (h_stage[k]) (void)hipHostFree(h_stage[k]);
+            if (done[k]) (void)hipEventDestroy(done[k]);
+        }
+    }
+};
 
 // A prepared scene (spt_scene_create): device AoS copy for the per-block LDS
 // staging, device SoA + light list for scenes above the LDS budget.
@@ -1448,6 +1480,7 @@ struct spt_scene {
     // The most recent launch (written on the host by launch(), read by spt_scene_info).
     struct LastLaunch { int count = 0, wpb = 0, nblocks = 0, cg = 0, n1 = 0, n2 = 0, dual = 0, lds = 0; };
     mutable LastLaunch last;
+    std::unique_ptr<SceneRefit> refit; // spt_scene_update_async's state (null until the first update)
 };
 
 namespace {
@@ -1759,6 +1792,215 @@ extern "C" int spt_scene_release_captures(const spt_scene *sc)
     if (!sc) return rtrt::fail(RT_ERR_INVALID, "spt_scene_release_captures: null scene");
     std::lock_guard<std::mutex> lk(sc->work.mu);
     sc->work.captured = 0;
+    return RT_OK;
+}
+
+// ---- in-place update (spt_refit.h)
+namespace {
+
+// vec.h:44 viszero, x tested twice: spt_scene_create's rule for a light.
+bool is_emitter(const rt_sphere &q) { return !((q.e.x == 0.f) && (q.e.x == 0.f) && (q.e.z == 0.f)); }
+
+// The first update of a scene: staging slots, the light index array and, for
+// a hierarchy scene, the topology.  The builders run once more on the scene
+// as it was created (sc->host still is that scene; they are deterministic), so
+// spt_scene_create keeps nothing for a scene that is never updated.
+int refit_prepare(spt_scene *sc)
+{
+    std::unique_ptr<SceneRefit> r(new SceneRefit());
+    const int n = sc->n;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < SceneRefit::SLOTS && e == hipSuccess; k++) {
+        e = hipHostMalloc((void **)&r->h_stage[k], (sizeof(rt_sphere) + sizeof(int)) * (size_t)n, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&r->done[k], hipEventDisableTiming);
+    }
+    if (e == hipSuccess) e = hipMalloc(&r->d_lights, sizeof(int) * (size_t)n);
+    if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_update_async staging");
+    r->light_cap = std::max(1, sc->nlights);
+    if (sc->bvh.node) {
+        std::vector<int> always;
+        sptbvh::BvhBuild b;
+        sptbvh::partition_and_build(sc->host.data(), n, always, b);
+        sptbvh::WideBuild wb;
+        if (sc->leaf_max) {
+            wb.leaf_max = sc->leaf_max;
+            wb.build(b);
+        }
+        sptrefit::Meta &m = r->meta;
+        if ((int)b.nodes.size() != sc->bvh.nnodes || (int)always.size() != sc->bvh.nalways ||
+            (sc->leaf_max ? wb.nnodes : 0) != sc->bvh.wnodes ||
+            !sptrefit::build_meta(b, (int)always.size(), sc->leaf_max ? wb.words.data() : nullptr, wb.nnodes, m))
+            return rtrt::fail(RT_ERR_INVALID, "spt_scene_update_async: the scene's topology cannot be rebuilt");
+        std::vector<int> ints;
+        ints.reserve(m.ints());
+        for (const std::vector<int> *v : {&m.range, &m.pos, &m.order, &m.wslot}) ints.insert(ints.end(), v->begin(), v->end());
+        const size_t planes = (6 * (size_t)m.nb + 3) & ~(size_t)3;
+        e = hipMalloc(&r->d_meta, sizeof(int) * ints.size());
+        if (e == hipSuccess) e = hipMalloc(&r->d_scratch, sizeof(float) * (planes + 8 * (size_t)m.nn));
+        if (e == hipSuccess) e = hipMemcpy(r->d_meta, ints.data(), sizeof(int) * ints.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_update_async metadata upload");
+        r->meta_bytes = sizeof(int) * ints.size() + sizeof(float) * (6 * (size_t)m.nb + 8 * (size_t)m.nn);
+    }
+    sc->refit = std::move(r);
+    return RT_OK;
+}
+
+// The device views the refit kernels take.
+sptrefit::DevRefit refit_view(const spt_scene &sc)
+{
+    const SceneRefit &r = *sc.refit;
+    const sptrefit::Meta &m = r.meta;
+    sptrefit::DevRefit v = {};
+    v.spheres = sc.d_spheres;
+    v.soa = sc.d_soa;
+    v.n = sc.n;
+    if (!sc.bvh.node) return v;
+    v.nodes = const_cast<float4 *>(sc.bvh.node);
+    v.geo = const_cast<float4 *>(sc.bvh.geo);
+    v.ids = sc.bvh.id;
+    v.wwords = (uint32_t *)const_cast<uint4 *>(sc.bvh.wnode);
+    v.nn = m.nn; v.nb = m.nb; v.na = m.na; v.wn = m.wn;
+    v.range = r.d_meta;
+    v.pos = v.range + m.range.size();
+    v.order = v.pos + m.pos.size();
+    v.wslot = v.order + m.order.size();
+    v.n_small = m.n_small; v.n_wave = m.n_wave; v.n_block = m.n_block;
+    v.box = r.d_scratch;
+    v.nbox = (float4 *)(r.d_scratch + ((6 * (size_t)m.nb + 3) & ~(size_t)3));
+    return v;
+}
+
+}  // namespace
+
+extern "C" int spt_scene_update_async(spt_scene *sc, const rt_sphere *spheres, unsigned first, unsigned count,
+                                      void *stream)
+{
+    if (!sc || !spheres) return rtrt::fail(RT_ERR_INVALID, "spt_scene_update_async: null pointer");
+    if (first > (unsigned)sc->n || count > (unsigned)sc->n - first)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_update_async: range out of bounds");
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(s, &cap);
+    if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_update_async stream");
+    if (cap != hipStreamCaptureStatusNone)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_update_async: the stream is capturing");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != sc->device)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_update_async: the scene's device is not the current one");
+    if (count == 0) return RT_OK;
+    int rc;
+    if (!sc->refit && (rc = refit_prepare(sc))) return rc;
+    SceneRefit &r = *sc->refit;
+    const int n = sc->n;
+
+    // The light list and no_refr of the edited scene, by spt_scene_create's
+    // rules -- the list only if the range held or holds an emitter.
+    bool lights_touched = false;
+    for (unsigned i = 0; i < count; i++)
+        lights_touched = lights_touched || is_emitter(sc->host[first + i]) || is_emitter(spheres[i]);
+    const int slot = r.next;
+    if (r.used[slot] && (e = hipEventSynchronize(r.done[slot])) != hipSuccess)   // (the update two calls back: long done)
+        return rtrt::fail_hip(e, "spt_scene_update_async staging wait");
+    rt_sphere *h_sp = (rt_sphere *)r.h_stage[slot];
+    int *h_lights = (int *)(r.h_stage[slot] + sizeof(rt_sphere) * (size_t)n);
+    std::copy(spheres, spheres + count, h_sp);
+    std::copy(spheres, spheres + count, sc->host.begin() + first);
+    int nl = sc->nlights;
+    if (lights_touched) {
+        nl = 0;
+        for (int i = 0; i < n; i++)
+            if (is_emitter(sc->host[i])) h_lights[nl++] = i;
+    }
+    sc->no_refr = std::all_of(sc->host.begin(), sc->host.end(), [](const rt_sphere &q) {
+        return is_emitter(q) || q.refl == 0 || q.refl == 1;
+    });
+    if (nl > r.light_cap) {
+        // More lights than d_soa has records for: a larger array.  The one
+        // path that synchronises (launches on other streams may still read
+        // the old array, and hipFree waits for them).
+        const int cap2 = std::max(nl, 2 * r.light_cap);
+        float4 *soa2 = nullptr;
+        e = hipMalloc(&soa2, sizeof(float4) * (3 * (size_t)n + 3 * (size_t)cap2));
+        if (e == hipSuccess) e = hipMemcpyAsync(soa2, sc->d_soa, sizeof(float4) * 3 * (size_t)n, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess) e = hipFree(sc->d_soa);
+        if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_update_async light records");
+        sc->d_soa = soa2;
+        r.light_cap = cap2;
+        r.reallocs++;
+    }
+    sc->nlights = nl;
+
+    e = hipMemcpyAsync(sc->d_spheres + first, h_sp, sizeof(rt_sphere) * (size_t)count, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && lights_touched && nl)
+        e = hipMemcpyAsync(r.d_lights, h_lights, sizeof(int) * (size_t)nl, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_update_async copy");
+    const sptrefit::DevRefit v = refit_view(*sc);
+    const bool tree = v.nodes != nullptr;
+    const int nrec = lights_touched ? std::max(1, nl) : 0;
+    // entry boxes: the whole scene at the first refit, the changed range after it
+    const int efirst = r.boxes_valid ? (int)first : 0, ecount = r.boxes_valid ? (int)count : n;
+    const int lanes = std::max({(int)count, tree ? v.nb + v.na : 0, nrec});
+    hipLaunchKernelGGL(sptrefit::refit_gather, dim3((lanes + 255) / 256), dim3(256), 0, s, v, (int)first, (int)count,
+                       efirst, ecount, r.d_lights, nl, nrec);
+    rc = rtrt::check_launch("spt refit_gather");
+    if (rc == RT_OK && tree) {
+        const int b_small = (v.n_small + 31) / 32, b_wave = (v.n_wave + 3) / 4;
+        hipLaunchKernelGGL(sptrefit::refit_nodes, dim3(b_small + b_wave + v.n_block), dim3(256), 0, s, v, b_small, b_wave);
+        rc = rtrt::check_launch("spt refit_nodes");
+        if (rc == RT_OK && v.wwords) {
+            hipLaunchKernelGGL(sptrefit::refit_wide, dim3((8 * v.wn + 255) / 256), dim3(256), 0, s, v);
+            rc = rtrt::check_launch("spt refit_wide");
+        }
+        if (rc == RT_OK) {
+            r.boxes_valid = true;
+            r.refits++;
+        }
+    }
+    e = hipEventRecord(r.done[slot], s);
+    if (rc == RT_OK && e != hipSuccess) rc = rtrt::fail_hip(e, "spt_scene_update_async record");
+    r.used[slot] = true;
+    r.next = (slot + 1) % SceneRefit::SLOTS;
+    if (rc == RT_OK) {
+        r.updates++;
+        if (lights_touched) r.light_rebuilds++;
+    }
+    return rc;
+}
+
+extern "C" int spt_scene_update_info(const spt_scene *sc, uint64_t *out, int nout)
+{
+    if (!sc || !out || nout < 1) return rtrt::fail(RT_ERR_INVALID, "spt_scene_update_info: bad arguments");
+    const SceneRefit *r = sc->refit.get();
+    const uint64_t v[SPT_UPDATE_INFO_WORDS] = {r ? r->updates : 0, r ? r->refits : 0, r ? r->light_rebuilds : 0,
+                                               r ? r->reallocs : 0, r ? r->meta_bytes : 0};
+    std::copy(v, v + std::min(nout, (int)SPT_UPDATE_INFO_WORDS), out);
+    return RT_OK;
+}
+
+extern "C" int spt_scene_read_hierarchy(const spt_scene *sc, void *out, size_t cap, size_t sizes[5])
+{
+    if (!sc || !sizes) return rtrt::fail(RT_ERR_INVALID, "spt_scene_read_hierarchy: null pointer");
+    const rt::smallpt::BvhView &v = sc->bvh;
+    for (int k = 0; k < 5; k++) sizes[k] = 0;
+    if (!v.node) return RT_OK;
+    const char *src[5] = {(const char *)v.node, (const char *)v.geo, (const char *)v.id, (const char *)v.wnode,
+                          (const char *)v.wmax};
+    sizes[0] = (size_t)(src[1] - src[0]);
+    sizes[1] = (size_t)(src[2] - src[1]);
+    sizes[2] = sizes[1] / 4;                                  // an int per float4 entry
+    sizes[3] = sizeof(uint32_t) * sptbvh::WIDE_WORDS * (size_t)v.wnodes;
+    sizes[4] = v.wnode ? sizeof(uint32_t) * sptbvh::WIDE * (size_t)v.wnodes : 0;
+    if (!out) return RT_OK;
+    if (cap < sizes[0] + sizes[1] + sizes[2] + sizes[3] + sizes[4])
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_read_hierarchy: buffer too small");
+    hipError_t e = hipDeviceSynchronize();
+    char *dst = (char *)out;
+    for (int k = 0; k < 5 && e == hipSuccess; k++) {
+        if (sizes[k]) e = hipMemcpy(dst, src[k], sizes[k], hipMemcpyDeviceToHost);
+        dst += sizes[k];
+    }
+    if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_read_hierarchy");
     return RT_OK;
 }
 

@@ -158,6 +158,20 @@ struct BvhBuild {
         return me;
     }
 
+    // Per node its range [lo, hi) of idx: build(lo, hi) covers exactly
+    // idx[lo..hi), the left child the lower part.  (Children have higher
+    // indices than their parent.)
+    void ranges(std::vector<int> &lo, std::vector<int> &hi) const
+    {
+        lo.assign(nodes.size(), 0);
+        hi.assign(nodes.size(), 0);
+        for (int i = (int)nodes.size() - 1; i >= 0; i--) {
+            const HostNode &h = nodes[i];
+            lo[i] = h.left < 0 ? h.first : lo[h.left];
+            hi[i] = h.left < 0 ? h.first + h.count : hi[h.right];
+        }
+    }
+
     // Depth-first layout for ray-direction octant `oct` (bit k set: d_k < 0):
     // at each inner node the child on the near side of its split axis comes
     // first; link = escape index (inner) or ~(first | count << 24) (leaf).

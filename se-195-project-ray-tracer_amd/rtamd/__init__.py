@@ -22,7 +22,7 @@ import numpy as np
 
 from . import ppm, scenes
 from .device import SmallptDeviceFrame
-from ._lib import (Camera, Float4, Primitive, QPrimitive, RTError, Sphere, Vec3, check, device_count, lib,
+from ._lib import (Camera, Float4, Primitive, QPrimitive, RTError, Sphere, Vec3, check, device_count, entry, lib,
                    set_device, SPT_COST_MAX, SPT_COUNT_RAYS, SPT_LIST_SET, SPT_DIRECT_LIGHTING, SPT_PATH_TRACING)
 
 __all__ = ["Camera", "Primitive", "QPrimitive", "Float4", "Sphere", "Vec3", "RTError", "scenes", "lib", "check",
@@ -139,6 +139,52 @@ class SmallptScene:
         d["no_refr"], d["two_query"] = bool(d["no_refr"]), bool(d["two_query"])
         return d
 
+    def update(self, spheres, first=0, count=None, stream=None):
+        """Replaces spheres [first, first + count) with spheres[0 .. count) in
+        place (spt_scene_update_async): asynchronous on `stream` (a torch
+        stream or a raw handle; default: torch's current stream where torch
+        is loaded, else the null stream), a hierarchy is refitted on the
+        device.  `spheres` is a Sphere array, or a pointer to one (then give
+        count); it is free again when the call returns.  count defaults to the
+        array's length."""
+        if count is None:
+            count = len(spheres)
+        if stream is None:
+            import sys
+            torch = sys.modules.get("torch")
+            stream = torch.cuda.current_stream() if torch is not None and torch.cuda.is_initialized() else None
+        stream = getattr(stream, "cuda_stream", stream)
+        ptr = None if spheres is None else C.cast(spheres, C.c_void_p)
+        check(entry("spt_scene_update_async")(self.handle, ptr, first, count, stream))
+
+    # spt_scene_update_info's words in order
+    UPDATE_INFO = ("updates", "refits", "light_rebuilds", "reallocations", "metadata_bytes")
+
+    def update_info(self):
+        """Host bookkeeping of update() (spt_scene_update_info): a dict keyed by UPDATE_INFO."""
+        out = (C.c_uint64 * len(self.UPDATE_INFO))()
+        check(entry("spt_scene_update_info")(self.handle, out, len(out)))
+        return dict(zip(self.UPDATE_INFO, (int(v) for v in out)))
+
+    def hierarchy(self):
+        """The hierarchy as the device holds it (spt_scene_read_hierarchy;
+        waits for the device): "nodes" float32 [16 x binary nodes, 4] (the
+        eight octant layouts, two rows per record), "geo" float32 [entries, 4],
+        "ids" int32 [entries], "wide" uint32 [8-wide nodes, 28], "maxid" uint32
+        [8-wide nodes, 8]; every array empty for a scene without one."""
+        read = entry("spt_scene_read_hierarchy")
+        sizes = (C.c_size_t * 5)()
+        check(read(self.handle, None, 0, sizes))
+        raw = np.zeros(max(sum(sizes), 1), np.uint8)
+        check(read(self.handle, raw.ctypes.data, raw.nbytes, sizes))
+        kinds = (("nodes", np.float32, (-1, 4)), ("geo", np.float32, (-1, 4)), ("ids", np.int32, (-1,)),
+                 ("wide", np.uint32, (-1, 28)), ("maxid", np.uint32, (-1, 8)))
+        out, o = {}, 0
+        for (name, kind, shape), nbytes in zip(kinds, sizes):
+            out[name] = raw[o:o + nbytes].view(kind).reshape(shape)
+            o += nbytes
+        return out
+
     def close(self):
         if self.handle:
             lib().spt_scene_destroy(self.handle)
@@ -171,6 +217,13 @@ class SmallptMulti:
 
     def set_scene(self, spheres, nspheres):
         check(lib().spt_multi_set_scene(self.handle, C.addressof(spheres), nspheres))
+
+    def update_scene(self, spheres, first=0, count=None):
+        """SmallptScene.update on every band's scene, each on its band's
+        stream (spt_multi_update_scene): no band is re-prepared."""
+        if count is None:
+            count = len(spheres)
+        check(entry("spt_multi_update_scene")(self.handle, C.cast(spheres, C.c_void_p), first, count))
 
     def upload(self, seeds, colors=None):
         check(lib().spt_multi_upload(self.handle, colors.ctypes.data if colors is not None else None,

@@ -24,6 +24,7 @@ EXPORTS = ("rt_last_error", "rt_device_count", "rt_set_device", "rt_release", "r
            "spt_scene_create", "spt_scene_destroy", "spt_scene_info", "spt_scene_release_captures", "spt_scene_render_async", "spt_scene_render_groups_async",
            "spt_group_count", "spt_scene_render_list_async", "spt_groups_pack_async", "spt_groups_unpack_async",
            "spt_pack_pixels_async",
+           "spt_scene_update_async", "spt_scene_update_info", "spt_scene_read_hierarchy", "spt_multi_update_scene",
            "spt_multi_create", "spt_multi_destroy", "spt_multi_set_scene", "spt_multi_bands", "spt_multi_upload",
            "spt_multi_render_async", "spt_multi_gather_async", "spt_multi_sync", "spt_multi_download",
            "spt_multi_read_frame", "spt_multi_counters", "spt_multi_band_buffers", "spt_render_multi",
@@ -118,6 +119,11 @@ def lib():
         L.spt_groups_pack_async.argtypes = [vp, i, i, vp, i, vp, vp]
         L.spt_groups_unpack_async.argtypes = [vp, i, i, vp, i, vp, vp]
     L.spt_seed_fill.restype = None
+    if hasattr(L, "spt_scene_update_async"):
+        L.spt_scene_update_async.argtypes = [vp, vp, u, u, vp]
+        L.spt_scene_update_info.argtypes = [vp, vp, i]
+        L.spt_scene_read_hierarchy.argtypes = [vp, vp, C.c_size_t, vp]
+        L.spt_multi_update_scene.argtypes = [vp, vp, u, u]
     if hasattr(L, "spt_multi_create"):
         ip = C.POINTER(C.c_int)
         L.spt_multi_create.argtypes = [vp, u, i, i, vp, i, C.POINTER(vp)]
