@@ -28,12 +28,14 @@
 #include "rt_glibc_math.h"
 #include "spt_policy.h"
 #include "spt_layout.h"
+#include "spt_accept.h"
 
 namespace rt {
 namespace smallpt {
 
 using namespace sptlayout;               // the kernel families, variant predicates and LDS layout
-constexpr float EPS = 0.01f;             // geom.h:29
+namespace acc = sptaccept;               // the integer accept tests of query_bf / shadow_bf
+constexpr float EPS = acc::EPS;          // geom.h:29
 constexpr float PI_F = 3.14159265358979323846f;
 constexpr int DIFF = 0, SPEC = 1;   // REFR = 2 is the remaining case
 #ifndef RT_SPT_QUNROLL
@@ -129,35 +131,112 @@ __device__ __forceinline__ int query(const G &geo, const ray3 &r, float &t, int 
 // The same query with a branch-free sphere test and the next sphere's record
 // loaded while the current one is tested (one LDS / scalar-load latency per
 // query instead of one per sphere).  sqrt_nr is exact for det in [2^-96,
-// inf); for det < 0 or NaN it returns NaN, and NaN roots fail both "> EPS"
-// tests -- the reference's miss; for det = +inf it returns NaN where sqrtf
-// returns +inf, whose root b + inf is never "< t" for the finite t of
-// every caller -- a miss either way.  Only |det| < 2^-96 (where sqrt_nr
-// is not sqrtf, e.g. det = +-0) is unsafe: any lane that meets one in the
-// whole query has the wave redo the query with the exact per-sphere test.
-template <bool COUNT, class G>
+// inf); for det < 0 or NaN it returns NaN, and NaN roots are no candidates --
+// the reference's miss; for det = +inf it returns NaN where sqrtf returns
+// +inf, whose root b + inf is never "< t" for the finite t of every caller --
+// a miss either way.  Only |det| < 2^-96 (where sqrt_nr is not sqrtf, e.g.
+// det = +-0) is unsafe: any lane that meets one in the whole query has the
+// wave redo the query with the exact per-sphere test.
+//
+// The accept tests run on integer keys (spt_accept.h): the bound is kept as a
+// limit key, a sphere's two roots and the bound fold into one unsigned three-
+// way minimum, "taken" is "the bound moved" (strict: a tie keeps the earlier,
+// higher index), and the distance is rebuilt from the bound once, after the
+// loop.  A t_in <= EPS or NaN accepts nothing and comes back unchanged.
+//
+// The loops are unrolled by hand -- trips of RT_SPT_QUNROLL spheres, then the
+// rest one by one -- because the compiler does not unroll a loop of unknown
+// length around the three-way minimum's instruction.  The |det| guard is one
+// minimum over the trip's spheres and one compare per trip.
+constexpr float DET_SAFE = 0x1p-96f;
+template <class G, class F, class T>
+__device__ __forceinline__ bool for_spheres_bf(const G &geo, const ray3 &r, F &&accept, T &&trip)
+{
+    // trip(k) before each run of k spheres, then accept(i, after, t1, t2) for
+    // i descending, `after` = the run's spheres still to come behind i (a
+    // constant once unrolled); true iff some |det| < DET_SAFE
+    const auto roots = [&](int i, float &t1, float &t2) {
+        const float4 g = geo.at(i);
+        const float opx = g.x - r.o.x, opy = g.y - r.o.y, opz = g.z - r.o.z;
+        const float b = opx * r.d.x + opy * r.d.y + opz * r.d.z;
+        const float det = b * b - (opx * opx + opy * opy + opz * opz) + g.w;
+        const float sd = sqrt_nr(det);
+        t1 = b - sd;
+        t2 = b + sd;
+        return fabsf(det);
+    };
+    bool bad = false;
+    int i = geo.count() - 1;
+#pragma unroll 1
+    for (; i >= RT_SPT_QUNROLL - 1; i -= RT_SPT_QUNROLL) {
+        float t1[RT_SPT_QUNROLL], t2[RT_SPT_QUNROLL];
+        float m = roots(i, t1[0], t2[0]);
+#pragma unroll
+        for (int j = 1; j < RT_SPT_QUNROLL; j++) m = __builtin_fminf(m, roots(i - j, t1[j], t2[j]));
+        trip(RT_SPT_QUNROLL);
+#pragma unroll
+        for (int j = 0; j < RT_SPT_QUNROLL; j++) accept(i - j, RT_SPT_QUNROLL - 1 - j, t1[j], t2[j]);
+        bad = bad || m < DET_SAFE;
+    }
+#pragma unroll 1
+    for (; i >= 0; i--) {
+        float t1, t2;
+        bad = bad || roots(i, t1, t2) < DET_SAFE;
+        trip(1);
+        accept(i, 0, t1, t2);
+    }
+    return bad;
+}
+
+// Returns the last updated index, negative if none.  KEYED (spt_layout.h
+// key_accept): false keeps the float form of the accept tests for the two
+// variants that the keyed form costs registers.
+// Uncounted, the keyed form does not select the loop's index (a scalar: one
+// v_mov per sphere to make it selectable) but counts the spheres that follow
+// the taken one: `since` grows by a trip's length before the trip and is set
+// to the constant `after` by the sphere that is taken.  The loop ends at
+// index 0, so the count is the index; untaken, it stays negative.
+template <bool COUNT, bool KEYED, class G>
 __device__ __forceinline__ int query_bf(const G &geo, const ray3 &r, float &t, int &first)
 {
     const float t_in = t;
     int id = -1;
     bool bad = false;
+    if constexpr (KEYED && COUNT) {
+        uint32_t tb = acc::limit_key(t_in);
+        bad = for_spheres_bf(geo, r, [&](int i, int, float t1, float t2) {
+            const bool take = acc::nearest_accept(tb, t1, t2);
+            id = take ? i : id;
+            first = (first < 0 && take) ? i : first;
+        }, [](int) {});
+        t = acc::nearest_result(tb, t_in);
+    } else if constexpr (KEYED) {
+        uint32_t tb = acc::limit_key(t_in);
+        int since = -(1 << 30);
+        bad = for_spheres_bf(geo, r, [&](int, int after, float t1, float t2) {
+            since = acc::nearest_accept(tb, t1, t2) ? after : since;
+        }, [&](int k) { since += k; });
+        id = since;
+        t = acc::nearest_result(tb, t_in);
+    } else {
 #pragma unroll RT_SPT_QUNROLL
-    for (int i = geo.count() - 1; i >= 0; i--) {
-        const float4 g = geo.at(i);
-        const float opx = g.x - r.o.x, opy = g.y - r.o.y, opz = g.z - r.o.z;
-        const float b = opx * r.d.x + opy * r.d.y + opz * r.d.z;
-        const float det = b * b - (opx * opx + opy * opy + opz * opz) + g.w;
-        bad = bad || fabsf(det) < 0x1p-96f;
-        const float sd = sqrt_nr(det);
-        const float t1 = b - sd, t2 = b + sd;
-        // SphereIntersect's distance is t1 if t1 > EPS, else t2 if t2 > EPS,
-        // else a miss: d = t1 > EPS ? t1 : t2, taken iff d > EPS && d < t
-        // (false for NaN) -- one select fewer than materialising the miss.
-        const float d = t1 > EPS ? t1 : t2;
-        const bool take = d > EPS && d < t;
-        t = take ? d : t;
-        id = take ? i : id;
-        if (COUNT) first = (first < 0 && take) ? i : first;
+        for (int i = geo.count() - 1; i >= 0; i--) {
+            const float4 g = geo.at(i);
+            const float opx = g.x - r.o.x, opy = g.y - r.o.y, opz = g.z - r.o.z;
+            const float b = opx * r.d.x + opy * r.d.y + opz * r.d.z;
+            const float det = b * b - (opx * opx + opy * opy + opz * opz) + g.w;
+            bad = bad || fabsf(det) < DET_SAFE;
+            const float sd = sqrt_nr(det);
+            const float t1 = b - sd, t2 = b + sd;
+            // SphereIntersect's distance is t1 if t1 > EPS, else t2 if t2 > EPS,
+            // else a miss: d = t1 > EPS ? t1 : t2, taken iff d > EPS && d < t
+            // (false for NaN) -- one select fewer than materialising the miss.
+            const float d = t1 > EPS ? t1 : t2;
+            const bool take = d > EPS && d < t;
+            t = take ? d : t;
+            id = take ? i : id;
+            if (COUNT) first = (first < 0 && take) ? i : first;
+        }
     }
     if (wave_any(bad)) {
         t = t_in;
@@ -236,20 +315,12 @@ __device__ __forceinline__ void query2_bf(const G &geo, const ray3 &r, float &t,
 template <class G>
 __device__ __forceinline__ bool shadow_bf(const G &geo, const ray3 &rs, float maxt, bool have)
 {
-    bool bad = false, occ = false;
-#pragma unroll RT_SPT_QUNROLL
-    for (int i = geo.count() - 1; i >= 0; i--) {
-        const float4 g = geo.at(i);
-        const float opx = g.x - rs.o.x, opy = g.y - rs.o.y, opz = g.z - rs.o.z;
-        const float b = opx * rs.d.x + opy * rs.d.y + opz * rs.d.z;
-        const float det = b * b - (opx * opx + opy * opy + opz * opz) + g.w;
-        bad = bad || (have && fabsf(det) < 0x1p-96f);
-        const float sd = sqrt_nr(det);
-        const float t1 = b - sd, t2 = b + sd;
-        const float d = t1 > EPS ? t1 : t2;
-        occ = occ || (d > EPS && d < maxt);
-    }
-    if (wave_any(bad)) {
+    // (spt_accept.h: the minimum key over every sphere's roots, then one
+    // compare against maxt's limit key -- 0, nothing passes, for maxt <= EPS)
+    uint32_t near = acc::KEY_NONE;
+    const bool bad = for_spheres_bf(geo, rs, [&](int, int, float t1, float t2) { acc::any_accept(near, t1, t2); }, [](int) {});
+    bool occ = acc::any_result(near, maxt);
+    if (wave_any(have && bad)) {
         float ts = maxt;
         int first = -1;
         occ = query<false>(geo, rs, ts, first) >= 0;
@@ -819,7 +890,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
             bool pushed = false;            // DQ: the lane pushed a shadow ray in this iteration
             if constexpr (DQ) {
                 id = -1;
-                if (live) id = query_bf<COUNT>(geo, ray, t, first);
+                if (live) id = query_bf<COUNT, V.key_accept()>(geo, ray, t, first);
                 // What this lane's shading is about to do that an unresolved
                 // entry must precede: add an emitter term, end its sample, push.
                 bool f_emit = false, f_ends = false, f_diff = false;
@@ -905,7 +976,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                         done = fin;
                     }
                 } else {
-                    id = query_bf<COUNT>(geo, ray, t, first);
+                    id = query_bf<COUNT, V.key_accept()>(geo, ray, t, first);
                 }
             } else if constexpr (GEO == GEO_BVH) {
                 // Resumable walk: a lane whose query needs more than this
@@ -934,7 +1005,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                 id = walk.id;
                 first = id;                 // any hit: the highest occluder (COUNT)
             } else {
-                id = query_bf<COUNT>(geo, ray, t, first);
+                id = query_bf<COUNT, V.key_accept()>(geo, ray, t, first);
             }
             float dp = 0.f, inv_sign = 1.f;  // REFR (pass A): vdot(normal, ray.d), -1 * sign(dp); and id
             if (DQ && !live) {

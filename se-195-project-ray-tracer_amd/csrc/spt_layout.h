@@ -56,6 +56,13 @@ struct Variant {
     // one-query global-memory kernels, which the register would take from 80
     // VGPRs to 81 and from six waves per SIMD to five)
     SPT_HD constexpr bool held_addr() const { return park() && !(geo == GEO_GLOBAL && cmode == CNT_FULL && !dual); }
+    // the one-ray queries' accept tests run on integer keys (spt_accept.h);
+    // else: on floats -- the two-query global-memory kernels that keep
+    // counters, where the keyed form costs the counted one two VGPRs and its
+    // sixth wave per SIMD (79 -> 81) and puts two more v_readlane into the
+    // RAYS one's loop; their one-ray query runs only in iterations without a
+    // shadow ray
+    SPT_HD constexpr bool key_accept() const { return park() && !(geo == GEO_GLOBAL && dual && cmode != CNT_NONE); }
     SPT_HD constexpr bool persist() const { return geo == GEO_WIDE; }              // waves fetch tiles from a work counter
     SPT_HD constexpr bool sched() const { return geo == GEO_BVH || geo == GEO_WIDE; }   // group order / cost code
     SPT_HD constexpr bool gstore() const { return geo == GEO_BVH; }                // stores staged per tile group

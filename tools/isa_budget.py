@@ -10,7 +10,7 @@ Each instruction is attributed twice through its `.loc` inlining chain:
            hit), pass A (light sample / refraction), done (running average),
            prologue / epilogue (outside the loop);
   op    -- the innermost frame that is one of the costed operations: RNG
-           draw, sphere test (query_bf / query2_bf body), sqrt_nr / rsq,
+           draw, sphere test (for_spheres_bf / query_bf / query2_bf body), sqrt_nr / rsq,
            rcp_nr, exact sqrt fallback, inv_len (vnorm), sincosf, powf
            (toInt), other.
 Counts are static (instructions in the code, each executed once per pass of
@@ -44,8 +44,8 @@ def ranges(path):
     phases = [("pass B", pb, q0), ("query", q0, hit), ("hit", hit, pa), ("pass A (>1 light)", multi, multi + 1),
               ("pass A", pa, done), ("done", done, end)]
     ops = [("RNG draw", find(r"float get_random_f\("), find(r"float get_random\(") + 3),
-           ("sphere test (exact fallback)", find(r"float sphere_hit\("), find(r"int query_bf\(const G") - 1),
-           ("sphere test", find(r"int query_bf\(const G"), find(r"^// ---------------------------------------------------------------------------", find(r"void query2_bf\("))),
+           ("sphere test (exact fallback)", find(r"float sphere_hit\("), find(r"bool for_spheres_bf\(const G") - 1),
+           ("sphere test", find(r"bool for_spheres_bf\(const G"), find(r"^// ---------------------------------------------------------------------------", find(r"void query2_bf\("))),
            ("vnorm/inv_len", find(r"v3 vnorm\("), find(r"v3 vnorm\(")),
            ("toInt", find(r"int to_int\(float x\)"), find(r"int to_int\(float x\)") + 4)]
     return (loop, end), phases, ops
