@@ -346,6 +346,45 @@ int spt_groups_unpack_async(float *d_colors, int w, int h, const int *d_groups, 
 int spt_pack_pixels_async(const float *d_colors, uint32_t *d_pixels, int w, int h, int row_begin,
                           int row_end, void *stream);
 
+/* ------------------------------------------------------------ smallpt, ray queries */
+/* What does this ray hit?  Caller-supplied rays against a prepared scene's
+ * current spheres, with the loops and hierarchy walks rendering uses.
+ *
+ * d_rays: device memory, 6 floats per ray (o.xyz, d.xyz), used as given: the
+ * direction is NOT normalised, and a direction of any length is exact.
+ * d_tmax: device memory, one float per ray -- maxt for ANY and OCCLUDER
+ * (required); for NEAREST the initial bound, NULL meaning 1e20f, which is
+ * Intersect.  d_t, d_id: device memory, one element per ray; they must not
+ * alias the inputs.  NEAREST writes whichever of the two is given (at least
+ * one); ANY and OCCLUDER write d_id, which they require, and never d_t.
+ *
+ * With d_i the float distance of SphereIntersect (geomfunc.h:32-59: its
+ * operations in its order, unfused, correctly rounded square root; 0 = miss)
+ * for sphere i, and the accepted set A = { i : d_i != 0 && d_i < bound }:
+ *   NEAREST   d_id[r] = the i in A of smallest d_i, ties to the highest index,
+ *             or -1; d_t[r] = that d_i, or on a miss the bound's own bits.
+ *   ANY       d_id[r] = 1 if A is not empty, else 0 (IntersectP's answer).
+ *   OCCLUDER  d_id[r] = the highest i in A (where IntersectP's descending
+ *             loop returns), or -1.
+ * These are the results of a full scan of all spheres, bit for bit, whichever
+ * kernel family the scene runs.  Any float may stand anywhere: a ray with a
+ * non-finite component hits nothing (the formula's own outcome), and a bound
+ * that is <= EPS (0.01f) or NaN accepts nothing.
+ *
+ * Asynchronous on `stream`; allocates nothing, never synchronises and takes
+ * no work-counter entry, so any number of calls may be captured into graphs.
+ * Ordered after earlier spt_scene_update_async calls on the same stream: a
+ * query enqueued after an update sees the edited spheres.  nrays == 0 is
+ * RT_OK and launches nothing.  RT_ERR_INVALID: a null scene or d_rays, an
+ * unknown kind, no output the kind writes, a missing d_tmax where required,
+ * nrays above INT32_MAX, another current device.
+ * RT_SPT_QUERY_BLOCKS=<n> (read at the call) caps the grid, for tests. */
+#define SPT_QUERY_NEAREST  0  /* Intersect,  geomfunc.h:71-92 */
+#define SPT_QUERY_ANY      1  /* IntersectP, geomfunc.h:94-110: occluded or not */
+#define SPT_QUERY_OCCLUDER 2  /* IntersectP's exit position: the highest-index occluder */
+int spt_scene_query_async(const spt_scene *scene, const float *d_rays, const float *d_tmax, size_t nrays,
+                          int kind, float *d_t, int *d_id, void *stream);
+
 /* ------------------------------------------------------------ smallpt, several GPUs */
 /* One frame tiled over the GPUs of a node in row bands:
  * band k owns the k-th contiguous chunk of the flipped colour / seed slots,

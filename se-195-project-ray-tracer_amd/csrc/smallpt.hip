@@ -1480,6 +1480,11 @@ __global__ void __launch_bounds__(256) list_dedup_kernel(const int *__restrict__
     }
 }
 
+// Ray queries on a prepared scene (spt_scene_query_async): kernels of their
+// own over the sphere loops and the walks of spt_walk.h; render_kernel does
+// not use them.
+#include "spt_query.h"
+
 }  // namespace smallpt
 }  // namespace rt
 
@@ -2073,6 +2078,62 @@ extern "C" int spt_scene_read_hierarchy(const spt_scene *sc, void *out, size_t c
     }
     if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_read_hierarchy");
     return RT_OK;
+}
+
+// ---- ray queries (spt_query.h)
+namespace {
+using QueryKernel = decltype(&rt::smallpt::query_kernel<0, 0>);
+
+template <int GEO>
+QueryKernel pick_query(int kind)
+{
+    if (kind == SPT_QUERY_ANY) return rt::smallpt::query_kernel<GEO, SPT_QUERY_ANY>;
+    if (kind == SPT_QUERY_OCCLUDER) return rt::smallpt::query_kernel<GEO, SPT_QUERY_OCCLUDER>;
+    return rt::smallpt::query_kernel<GEO, SPT_QUERY_NEAREST>;
+}
+}  // namespace
+
+extern "C" int spt_scene_query_async(const spt_scene *sc, const float *d_rays, const float *d_tmax, size_t nrays,
+                                     int kind, float *d_t, int *d_id, void *stream)
+{
+    static_assert(rt::smallpt::Q_NEAREST == SPT_QUERY_NEAREST && rt::smallpt::Q_ANY == SPT_QUERY_ANY &&
+                  rt::smallpt::Q_OCCLUDER == SPT_QUERY_OCCLUDER, "rt_hip.h's query kinds");
+    if (!sc || !d_rays) return rtrt::fail(RT_ERR_INVALID, "spt_scene_query_async: null scene or rays");
+    if (kind != SPT_QUERY_NEAREST && kind != SPT_QUERY_ANY && kind != SPT_QUERY_OCCLUDER)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_query_async: unknown kind");
+    if (!d_t && !d_id) return rtrt::fail(RT_ERR_INVALID, "spt_scene_query_async: no output");
+    if (kind != SPT_QUERY_NEAREST && (!d_tmax || !d_id))
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_query_async: an occlusion query needs d_tmax and d_id");
+    if (nrays > (size_t)INT32_MAX) return rtrt::fail(RT_ERR_INVALID, "spt_scene_query_async: too many rays");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != sc->device)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_query_async: the scene's device is not the current one");
+    if (nrays == 0) return RT_OK;
+    // The family rendering picks (scene_geo); the LDS family always fits here
+    // (the geo records alone: a third of the scene copy it was admitted by).
+    const int geo = scene_geo(*sc);
+    const bool counted = kind == SPT_QUERY_OCCLUDER;
+    const SceneSizes sizes{sc->n, sc->nlights, sc->bvh.wnodes, sc->bvh.wdepth};
+    const size_t lds = query_lds_bytes(geo, sizes, counted);
+    const int wpb = query_wpb(geo);
+    // Persistent blocks: one per CU for the 8-wide family (its LDS copy of the
+    // tree), else up to QUERY_BLOCKS_PER_CU; fewer for a small batch.
+    // RT_SPT_QUERY_BLOCKS=<n> caps the grid (tests: several rounds per block).
+    constexpr int QUERY_BLOCKS_PER_CU = 8;
+    const long long nchunks = ((long long)nrays + 63) / 64;
+    long long nblocks = std::min<long long>((nchunks + wpb - 1) / wpb,
+                                            (long long)sc->cus * (geo == GEO_WIDE ? 1 : QUERY_BLOCKS_PER_CU));
+    if (const char *cap = getenv("RT_SPT_QUERY_BLOCKS")) nblocks = std::min<long long>(nblocks, std::max(atoi(cap), 1));
+    // wide_walk: no early return (stop 0), the leaf batch threshold rendering uses
+    const int opts = sptpolicy::pack_split(0, false, 0, 255, sptpolicy::SptTune().batch, 0);
+    const rt::smallpt::QueryArgs a{d_rays, d_tmax, kind == SPT_QUERY_NEAREST ? d_t : nullptr, d_id, (int)nrays, sc->n,
+                                   sc->d_soa, opts};
+    const QueryKernel kern = geo == GEO_WIDE  ? pick_query<GEO_WIDE>(kind)
+                             : geo == GEO_BVH ? pick_query<GEO_BVH>(kind)
+                             : geo == GEO_LDS ? pick_query<GEO_LDS>(kind)
+                                              : pick_query<GEO_GLOBAL>(kind);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * wpb), lds, (hipStream_t)stream, a, sc->bvh);
+    return rtrt::check_launch("spt query_kernel");
 }
 
 namespace {

@@ -159,6 +159,21 @@ SPT_HD constexpr int launch_geo(Variant v, const SceneSizes &s, int wpb)
     return (v.geo == GEO_LDS && block_lds_bytes(v, s, wpb) > (size_t)CU_LDS_BYTES) ? GEO_GLOBAL : v.geo;
 }
 
+// ---- ray queries (spt_query.h's query_kernel): blocks of QUERY_WPB waves, 16
+// for the 8-wide family -- the shape its tree was budgeted for (spt_bvh.h
+// choose_wide), so nodes, highest-index table and stacks fit WIDE_LDS_MAX.
+// LDS family: the geo records alone at offset 0; 8-wide family: GEO_WIDE's
+// carve above, `counted` for the kind that seeks the highest-index occluder;
+// the other two families use none.
+constexpr int QUERY_WPB = 4, QUERY_WPB_WIDE = sptpolicy::WIDE_WPB;
+SPT_HD constexpr int query_wpb(int geo) { return geo == GEO_WIDE ? QUERY_WPB_WIDE : QUERY_WPB; }
+SPT_HD constexpr size_t query_lds_bytes(int geo, const SceneSizes &s, bool counted)
+{
+    return geo == GEO_WIDE  ? wide_lds_bytes(s.wnodes, s.wdepth, QUERY_WPB_WIDE, counted)
+           : geo == GEO_LDS ? (size_t)RECORD_BYTES * s.n
+                            : 0;
+}
+
 }  // namespace sptlayout
 
 #endif

@@ -23,12 +23,14 @@ import numpy as np
 from . import ppm, scenes
 from .device import SmallptDeviceFrame
 from ._lib import (Camera, Float4, Primitive, QPrimitive, RTError, Sphere, Vec3, check, device_count, entry, lib,
-                   set_device, SPT_COST_MAX, SPT_COUNT_RAYS, SPT_LIST_SET, SPT_DIRECT_LIGHTING, SPT_PATH_TRACING)
+                   set_device, SPT_COST_MAX, SPT_COUNT_RAYS, SPT_LIST_SET, SPT_DIRECT_LIGHTING, SPT_PATH_TRACING,
+                   SPT_QUERY_ANY, SPT_QUERY_NEAREST, SPT_QUERY_OCCLUDER)
 
 __all__ = ["Camera", "Primitive", "QPrimitive", "Float4", "Sphere", "Vec3", "RTError", "scenes", "lib", "check",
            "device_count", "set_device", "whitted_render", "queue_render", "SmallptFrame", "SmallptScene",
            "SmallptMulti", "SmallptDeviceFrame",
-           "SPT_PATH_TRACING", "SPT_DIRECT_LIGHTING", "SPT_COUNT_RAYS", "SPT_COST_MAX", "SPT_LIST_SET"]
+           "SPT_PATH_TRACING", "SPT_DIRECT_LIGHTING", "SPT_COUNT_RAYS", "SPT_COST_MAX", "SPT_LIST_SET",
+           "SPT_QUERY_NEAREST", "SPT_QUERY_ANY", "SPT_QUERY_OCCLUDER"]
 
 
 def whitted_render(w, h, row_begin=20, row_end=None, prims=None, nprims=None, frame=None,
@@ -184,6 +186,60 @@ class SmallptScene:
             out[name] = raw[o:o + nbytes].view(kind).reshape(shape)
             o += nbytes
         return out
+
+    # query kinds by name (include/rt_hip.h SPT_QUERY_*)
+    QUERY_KINDS = {"nearest": SPT_QUERY_NEAREST, "any": SPT_QUERY_ANY, "occluder": SPT_QUERY_OCCLUDER}
+
+    def query(self, rays, tmax=None, kind="nearest", out=None, stream=None):
+        """What the rays hit (spt_scene_query_async): `rays` is a contiguous
+        float32 device tensor [n, 6] (o.xyz, d.xyz; the direction is used as
+        given), `tmax` a float32 device tensor [n] -- required for "any" and
+        "occluder", the optional initial bound of "nearest".  Returns (t, id):
+        "nearest" the distance (float32; on a miss the bound's bits) and the
+        sphere index or -1; "any" (None, 1 or 0); "occluder" (None, the highest
+        occluder's index or -1); id is int32.  out=(t, id) takes the caller's
+        tensors (for "nearest" either may be None; the occlusion kinds use
+        id only).  Asynchronous on `stream` (a torch stream or a raw handle;
+        default: torch's current stream); allocates only the outputs it was
+        not given."""
+        import torch
+        if kind not in self.QUERY_KINDS:
+            raise ValueError("query: kind %r is not one of %s" % (kind, sorted(self.QUERY_KINDS)))
+        if not (rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 6
+                and rays.is_contiguous()):
+            raise ValueError("query: rays must be a contiguous float32 device tensor [n, 6]")
+        n = rays.shape[0]
+        if tmax is not None and not (tmax.is_cuda and tmax.dtype == torch.float32 and tmax.numel() == n
+                                     and tmax.is_contiguous()):
+            raise ValueError("query: tmax must be a contiguous float32 device tensor [n]")
+        nearest = kind == "nearest"
+        if out is None:
+            t = torch.empty(n, dtype=torch.float32, device=rays.device) if nearest else None
+            ids = torch.empty(n, dtype=torch.int32, device=rays.device)
+        else:
+            t, ids = out
+            t = t if nearest else None
+            for x, dt in ((t, torch.float32), (ids, torch.int32)):
+                if x is not None and not (x.is_cuda and x.dtype == dt and x.numel() == n and x.is_contiguous()):
+                    raise ValueError("query: out must hold contiguous device tensors [n], float32 and int32")
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        stream = getattr(stream, "cuda_stream", stream)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        if n:                                                  # (an empty tensor has no address to pass)
+            check(entry("spt_scene_query_async")(self.handle, rays.data_ptr(), ptr(tmax), n, self.QUERY_KINDS[kind],
+                                                 ptr(t), ptr(ids), stream))
+        return t, ids
+
+    def pick(self, cam, w, h, x, y):
+        """The sphere under pixel (x, y) of a w x h view through `cam` -- the
+        pixel `pixels` holds at y * w + x: (id, t) of the pixel-centre camera
+        ray's nearest hit (scenes.camera_rays; id -1 on a miss).  Blocking."""
+        import torch
+        if not (0 <= x < w and 0 <= y < h):
+            raise ValueError("pick: pixel (%d, %d) outside %d x %d" % (x, y, w, h))
+        t, ids = self.query(torch.from_numpy(scenes.camera_rays(cam, w, h, [x], [y])).cuda())
+        return int(ids.cpu()[0]), float(t.cpu()[0])
 
     def close(self):
         if self.handle:

@@ -9,6 +9,7 @@ These are the reference's own host-side inputs (not part of the device path):
   * read_scene()     -- ReadScene .scn parser (displayfunc.cpp:120-180)
   * hypersphere()    -- scene_build_complex.pl generator (:3-60)
   * complex10k()     -- the 10k-sphere config (BASELINE configs[4])
+  * camera_rays()    -- GenerateCameraRay's pixel-centre rays (rendering_kernel.cl:29-51)
   * queue_scene()    -- Raytracer3.2.03 create_scene (scene.c:48-97, CHOOSE_SCENE 0)
                         after raytracer.c:721-746's copy into Primitive_2
 All float arithmetic is float32, in the reference's order.
@@ -228,6 +229,32 @@ def smallpt(kind, w, h):
         update_camera(cam, w, h)
         return arr, n, cam
     raise ValueError("smallpt scene %r: cornell or complex" % (kind,))
+
+
+def camera_rays(cam, w, h, x=None, y=None):
+    """GenerateCameraRay (rendering_kernel.cl:29-51, smallptCPU.cpp:77-100)
+    for every pixel with both draws taken as 0.5 (r1 = r2 = 0: the pixel's
+    centre): float32 [w * h, 6] rows of (o.xyz, d.xyz), the direction
+    normalised as vnorm does.  Row y * w + x is the ray of the pixel that
+    `pixels` holds at y * w + x.  With x and y (equally long integer arrays)
+    only those pixels' rays, in their order.  Float32 arithmetic, one operation
+    per numpy call, in the reference's order."""
+    inv_w, inv_h = f32(1.0) / f32(w), f32(1.0) / f32(h)
+    if x is None:
+        x, y = np.tile(np.arange(w), h), np.repeat(np.arange(h), w)
+    x, y = np.asarray(x).astype(f32), np.asarray(y).astype(f32)
+    kcx = (x + f32(0.0)) * inv_w - f32(0.5)
+    kcy = (y + f32(0.0)) * inv_h - f32(0.5)
+    rdir = [f32(getattr(cam.x, a)) * kcx + f32(getattr(cam.y, a)) * kcy + f32(getattr(cam.dir, a)) for a in "xyz"]
+    out = np.empty((len(x), 6), dtype=f32)
+    for k, a in enumerate("xyz"):
+        out[:, k] = f32(0.1) * rdir[k] + f32(getattr(cam.orig, a))
+    # vnorm (vec.h:50): l = 1.f / sqrt(dot); v = l * v
+    dot = rdir[0] * rdir[0] + rdir[1] * rdir[1] + rdir[2] * rdir[2]
+    l = f32(1.0) / np.sqrt(dot)
+    for k in range(3):
+        out[:, 3 + k] = l * rdir[k]
+    return out
 
 
 def seeds(width, height, seed=1):
