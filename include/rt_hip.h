@@ -385,6 +385,47 @@ int spt_pack_pixels_async(const float *d_colors, uint32_t *d_pixels, int w, int 
 int spt_scene_query_async(const spt_scene *scene, const float *d_rays, const float *d_tmax, size_t nrays,
                           int kind, float *d_t, int *d_id, void *stream);
 
+/* ------------------------------------------------------------ smallpt, radiance queries */
+/* What radiance arrives along this ray?  The reference's estimator on
+ * caller-supplied rays against a prepared scene's current spheres, in the
+ * kernel family the scene renders with.
+ *
+ * d_rays: device memory, 6 floats per ray (o.xyz, d.xyz), used as given and
+ * NOT normalised, as for spt_scene_query_async.  d_seeds_in / d_seeds_out:
+ * device memory, the ray's two MWC words (simplernd.h) at 2r and 2r + 1; the
+ * two may be the same buffer.  d_radiance: device memory, 3 floats per ray,
+ * the ray's running average: read and written when first_sample > 0, only
+ * written when first_sample == 0; it must not alias the rays or the seeds.
+ * mode: SPT_PATH_TRACING or SPT_DIRECT_LIGHTING, without flag bits.
+ *
+ * For ray r, with (s0, s1) read from d_seeds_in, for j = 0 .. nsamples - 1:
+ *   R = RadiancePathTracing(spheres, n, &ray_r, &s0, &s1)   geomfunc.h:167-338
+ *       (or RadianceDirectLighting, :340-483),
+ *   current = first_sample + j,
+ *   d_radiance[r] = current == 0 ? R : (d_radiance[r] * k1 + R) * k2 per
+ *       component, k1 = (float)current, k2 = 1.f / (k1 + 1.f)
+ *       (smallptCPU.cpp:110-118),
+ * and (s0, s1) is then written to d_seeds_out: bit for bit what the
+ * reference's functions return for that ray and state, whichever family the
+ * scene runs.  No camera draw is taken: a caller who wants the reference's
+ * pixel jitter draws it before the call.  A ray whose first Intersect misses
+ * -- every ray with a non-finite component among them -- yields (0, 0, 0)
+ * for that sample and draws nothing.  nsamples == 0 copies the seeds and
+ * leaves d_radiance alone.
+ *
+ * Asynchronous on `stream`; allocates nothing, never synchronises and takes
+ * no work-counter entry, so any number of calls may be captured into graphs.
+ * Ordered after earlier spt_scene_update_async calls on the same stream.
+ * nrays == 0 is RT_OK and launches nothing.  RT_ERR_INVALID: a null scene,
+ * d_rays, d_seeds_in, d_seeds_out or d_radiance, a negative nsamples or
+ * first_sample, an unknown mode or one carrying flag bits, nrays above
+ * INT32_MAX, another current device.
+ * RT_SPT_QUERY_BLOCKS=<n> (read at the call) caps the grid, for tests. */
+int spt_scene_radiance_async(const spt_scene *scene, const float *d_rays, size_t nrays,
+                             const uint32_t *d_seeds_in, uint32_t *d_seeds_out,
+                             float *d_radiance, int first_sample, int nsamples, int mode,
+                             void *stream);
+
 /* ------------------------------------------------------------ smallpt, several GPUs */
 /* One frame tiled over the GPUs of a node in row bands:
  * band k owns the k-th contiguous chunk of the flipped colour / seed slots,

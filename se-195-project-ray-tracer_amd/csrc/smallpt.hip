@@ -1485,6 +1485,10 @@ __global__ void __launch_bounds__(256) list_dedup_kernel(const int *__restrict__
 // not use them.
 #include "spt_query.h"
 
+// Radiance queries (spt_scene_radiance_async): the estimator along the
+// caller's rays, one path per lane over the same loops and walks.
+#include "spt_radiance.h"
+
 }  // namespace smallpt
 }  // namespace rt
 
@@ -2134,6 +2138,59 @@ extern "C" int spt_scene_query_async(const spt_scene *sc, const float *d_rays, c
                                               : pick_query<GEO_GLOBAL>(kind);
     hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * wpb), lds, (hipStream_t)stream, a, sc->bvh);
     return rtrt::check_launch("spt query_kernel");
+}
+
+// ---- radiance queries (spt_radiance.h)
+namespace {
+using RadianceKernel = decltype(&rt::smallpt::radiance_kernel<0, false>);
+
+template <int GEO>
+RadianceKernel pick_radiance(bool dl)
+{
+    return dl ? rt::smallpt::radiance_kernel<GEO, true> : rt::smallpt::radiance_kernel<GEO, false>;
+}
+}  // namespace
+
+extern "C" int spt_scene_radiance_async(const spt_scene *sc, const float *d_rays, size_t nrays,
+                                        const uint32_t *d_seeds_in, uint32_t *d_seeds_out, float *d_radiance,
+                                        int first_sample, int nsamples, int mode, void *stream)
+{
+    if (!sc || !d_rays || !d_seeds_in || !d_seeds_out || !d_radiance)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_radiance_async: null scene, rays, seeds or radiance");
+    if (nsamples < 0 || first_sample < 0)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_radiance_async: negative nsamples or first_sample");
+    if (mode != SPT_PATH_TRACING && mode != SPT_DIRECT_LIGHTING)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_radiance_async: unknown mode (no flags are taken)");
+    if (nrays > (size_t)INT32_MAX) return rtrt::fail(RT_ERR_INVALID, "spt_scene_radiance_async: too many rays");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != sc->device)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_radiance_async: the scene's device is not the current one");
+    if (nrays == 0) return RT_OK;
+    // The family rendering picks (scene_geo); an LDS-family scene whose copy
+    // would not fit a block reads the same records from global memory (with
+    // MAX_LDS_BYTES below a CU's LDS every admitted copy fits today).
+    const SceneSizes sizes{sc->n, sc->nlights, sc->bvh.wnodes, sc->bvh.wdepth};
+    int geo = scene_geo(*sc);
+    if (geo == GEO_LDS && radiance_lds_bytes(geo, sizes) > (size_t)CU_LDS_BYTES) geo = GEO_GLOBAL;
+    const size_t lds = radiance_lds_bytes(geo, sizes);
+    const int wpb = query_wpb(geo);
+    // query_kernel's grid: persistent blocks, one per CU for the 8-wide
+    // family, else up to RADIANCE_BLOCKS_PER_CU; RT_SPT_QUERY_BLOCKS caps it.
+    constexpr int RADIANCE_BLOCKS_PER_CU = 8;
+    const long long nchunks = ((long long)nrays + 63) / 64;
+    long long nblocks = std::min<long long>((nchunks + wpb - 1) / wpb,
+                                            (long long)sc->cus * (geo == GEO_WIDE ? 1 : RADIANCE_BLOCKS_PER_CU));
+    if (const char *cap = getenv("RT_SPT_QUERY_BLOCKS")) nblocks = std::min<long long>(nblocks, std::max(atoi(cap), 1));
+    const int opts = sptpolicy::pack_split(0, false, 0, 255, sptpolicy::SptTune().batch, 0);
+    const rt::smallpt::RadianceArgs a{d_rays, d_seeds_in, d_seeds_out, d_radiance, (int)nrays, first_sample, nsamples,
+                                      sc->n, sc->nlights, sc->d_soa, opts};
+    const bool dl = mode == SPT_DIRECT_LIGHTING;
+    const RadianceKernel kern = geo == GEO_WIDE  ? pick_radiance<GEO_WIDE>(dl)
+                                : geo == GEO_BVH ? pick_radiance<GEO_BVH>(dl)
+                                : geo == GEO_LDS ? pick_radiance<GEO_LDS>(dl)
+                                                 : pick_radiance<GEO_GLOBAL>(dl);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * wpb), lds, (hipStream_t)stream, a, sc->bvh);
+    return rtrt::check_launch("spt radiance_kernel");
 }
 
 namespace {

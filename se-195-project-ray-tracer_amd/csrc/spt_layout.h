@@ -174,6 +174,18 @@ SPT_HD constexpr size_t query_lds_bytes(int geo, const SceneSizes &s, bool count
                             : 0;
 }
 
+// ---- radiance queries (spt_radiance.h's radiance_kernel): query_kernel's
+// blocks.  LDS family: the whole scene copy -- geo | emi | col | lrec, as
+// render_kernel stages it -- at offset 0; 8-wide family: the uncounted
+// GEO_WIDE carve (nodes and stacks; the materials stay in global memory); the
+// other two families use none.
+SPT_HD constexpr size_t radiance_lds_bytes(int geo, const SceneSizes &s)
+{
+    return geo == GEO_WIDE  ? wide_lds_bytes(s.wnodes, s.wdepth, QUERY_WPB_WIDE, false)
+           : geo == GEO_LDS ? (size_t)scene_bytes(s.n, s.nlights)
+                            : 0;
+}
+
 }  // namespace sptlayout
 
 #endif

@@ -231,6 +231,52 @@ class SmallptScene:
                                                  ptr(t), ptr(ids), stream))
         return t, ids
 
+    def radiance(self, rays, seeds, nsamples=1, first_sample=0, mode=SPT_PATH_TRACING, out=None, seeds_out=None,
+                 stream=None):
+        """The reference's radiance along the rays (spt_scene_radiance_async):
+        `rays` as for query(); `seeds` a contiguous int32 device tensor [n, 2]
+        (SmallptDeviceFrame's seed dtype; the 32-bit patterns of the two MWC
+        words), each ray's RNG state.  Samples first_sample .. first_sample +
+        nsamples - 1 of RadiancePathTracing (or, mode=SPT_DIRECT_LIGHTING,
+        RadianceDirectLighting) are folded into the running average `out`
+        (float32 [n, 3]; read when first_sample > 0, so then required).
+        Returns (radiance, seeds): `out` or a new tensor, and the advanced
+        states in `seeds_out` (which may be `seeds` itself) or a new tensor.
+        Asynchronous on `stream` (a torch stream or a raw handle; default:
+        torch's current stream); allocates only the outputs it was not given."""
+        import torch
+        if not (rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 6
+                and rays.is_contiguous()):
+            raise ValueError("radiance: rays must be a contiguous float32 device tensor [n, 6]")
+        n = rays.shape[0]
+
+        def is_seeds(x):
+            return (x.is_cuda and x.dtype == torch.int32 and x.dim() == 2 and tuple(x.shape) == (n, 2)
+                    and x.is_contiguous())
+        if not is_seeds(seeds):
+            raise ValueError("radiance: seeds must be a contiguous int32 device tensor [n, 2]")
+        if seeds_out is not None and not is_seeds(seeds_out):
+            raise ValueError("radiance: seeds_out must be a contiguous int32 device tensor [n, 2]")
+        if out is not None and not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 3)
+                                    and out.is_contiguous()):
+            raise ValueError("radiance: out must be a contiguous float32 device tensor [n, 3]")
+        if nsamples < 0 or first_sample < 0:
+            raise ValueError("radiance: nsamples and first_sample must not be negative")
+        if out is None:
+            if first_sample > 0:
+                raise ValueError("radiance: first_sample > 0 continues the running average in out=")
+            out = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+        if seeds_out is None:
+            seeds_out = torch.empty_like(seeds)
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        stream = getattr(stream, "cuda_stream", stream)
+        if n:                                                  # (an empty tensor has no address to pass)
+            check(entry("spt_scene_radiance_async")(self.handle, rays.data_ptr(), n, seeds.data_ptr(),
+                                                    seeds_out.data_ptr(), out.data_ptr(), first_sample, nsamples,
+                                                    mode, stream))
+        return out, seeds_out
+
     def pick(self, cam, w, h, x, y):
         """The sphere under pixel (x, y) of a w x h view through `cam` -- the
         pixel `pixels` holds at y * w + x: (id, t) of the pixel-centre camera

@@ -9,7 +9,8 @@ These are the reference's own host-side inputs (not part of the device path):
   * read_scene()     -- ReadScene .scn parser (displayfunc.cpp:120-180)
   * hypersphere()    -- scene_build_complex.pl generator (:3-60)
   * complex10k()     -- the 10k-sphere config (BASELINE configs[4])
-  * camera_rays()    -- GenerateCameraRay's pixel-centre rays (rendering_kernel.cl:29-51)
+  * camera_rays()    -- GenerateCameraRay's pixel-centre or jittered rays (rendering_kernel.cl:29-51)
+  * mwc_draw()       -- GetRandom on arrays of states (simplernd.h:34-48)
   * queue_scene()    -- Raytracer3.2.03 create_scene (scene.c:48-97, CHOOSE_SCENE 0)
                         after raytracer.c:721-746's copy into Primitive_2
 All float arithmetic is float32, in the reference's order.
@@ -231,20 +232,37 @@ def smallpt(kind, w, h):
     raise ValueError("smallpt scene %r: cornell or complex" % (kind,))
 
 
-def camera_rays(cam, w, h, x=None, y=None):
+def mwc_draw(s0, s1):
+    """GetRandom (simplernd.h:34-48) on arrays of states: (value float32, s0,
+    s1) with the advanced states, the inputs untouched.  Exact: the words are
+    uint32 arithmetic, the value is the float in [2, 4) built from 23 bits,
+    then (f - 2) / 2 in float32."""
+    s0, s1 = np.atleast_1d(np.asarray(s0, dtype=np.uint32)), np.atleast_1d(np.asarray(s1, dtype=np.uint32))
+    s0 = np.uint32(36969) * (s0 & np.uint32(65535)) + (s0 >> np.uint32(16))
+    s1 = np.uint32(18000) * (s1 & np.uint32(65535)) + (s1 >> np.uint32(16))
+    ires = (s0 << np.uint32(16)) + s1                            # (array arithmetic: wraps at 2^32)
+    f = ((ires & np.uint32(0x007fffff)) | np.uint32(0x40000000)).view(f32)
+    return (f - f32(2.0)) / f32(2.0), s0, s1
+
+
+def camera_rays(cam, w, h, x=None, y=None, r1=None, r2=None):
     """GenerateCameraRay (rendering_kernel.cl:29-51, smallptCPU.cpp:77-100)
     for every pixel with both draws taken as 0.5 (r1 = r2 = 0: the pixel's
     centre): float32 [w * h, 6] rows of (o.xyz, d.xyz), the direction
     normalised as vnorm does.  Row y * w + x is the ray of the pixel that
     `pixels` holds at y * w + x.  With x and y (equally long integer arrays)
-    only those pixels' rays, in their order.  Float32 arithmetic, one operation
-    per numpy call, in the reference's order."""
+    only those pixels' rays, in their order.  r1, r2 (float32, one per ray):
+    the reference's jitter, the values GetRandom() - .5f (mwc_draw), applied
+    as kcx = (x + r1) * inv_w - .5.  Float32 arithmetic, one operation per
+    numpy call, in the reference's order."""
     inv_w, inv_h = f32(1.0) / f32(w), f32(1.0) / f32(h)
     if x is None:
         x, y = np.tile(np.arange(w), h), np.repeat(np.arange(h), w)
     x, y = np.asarray(x).astype(f32), np.asarray(y).astype(f32)
-    kcx = (x + f32(0.0)) * inv_w - f32(0.5)
-    kcy = (y + f32(0.0)) * inv_h - f32(0.5)
+    r1 = f32(0.0) if r1 is None else np.asarray(r1, dtype=f32)
+    r2 = f32(0.0) if r2 is None else np.asarray(r2, dtype=f32)
+    kcx = (x + r1) * inv_w - f32(0.5)
+    kcy = (y + r2) * inv_h - f32(0.5)
     rdir = [f32(getattr(cam.x, a)) * kcx + f32(getattr(cam.y, a)) * kcy + f32(getattr(cam.dir, a)) for a in "xyz"]
     out = np.empty((len(x), 6), dtype=f32)
     for k, a in enumerate("xyz"):
