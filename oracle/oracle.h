@@ -132,6 +132,10 @@ int  orq_scene_init(orq_primitive *out, int cap);
 void orq_render(const orq_primitive *P, int n, uint8_t *pixels, int w, int h, int row_begin, int row_end,
                 uint64_t *counters, int nthreads);
 
+/* Single primitive helper, exposed for unit tests (intersect, :95-160): the
+ * twin of orw_primitive_intersect. */
+int  orq_primitive_intersect(const orq_primitive *p, const float ray[6], float *dist);
+
 /* FNV-1a-64 over bytes, as used for the SURVEY.md §8(c) known answers. */
 uint64_t or_fnv1a64(const void *data, size_t nbytes);
 

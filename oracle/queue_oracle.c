@@ -78,6 +78,15 @@ static int q_intersect(const orq_primitive *p, const qray *ray, float *cumu)
     return 0;
 }
 
+int orq_primitive_intersect(const orq_primitive *p, const float ray[6], float *dist)
+{
+    qray r;
+    memset(&r, 0, sizeof(r));
+    r.o.x = ray[0]; r.o.y = ray[1]; r.o.z = ray[2];
+    r.d.x = ray[3]; r.d.y = ray[4]; r.d.z = ray[5];
+    return q_intersect(p, &r, dist);
+}
+
 /* get_normal, :162-177. */
 static orq_f4 q_normal(const orq_primitive *p, orq_f4 pt)
 {

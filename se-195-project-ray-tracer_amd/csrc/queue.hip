@@ -28,9 +28,9 @@
 //     rest are walked breadth-first through their child links (a 32-slot
 //     per-lane ring in LDS holds pool slots, not rays);
 //   * glibc's double pow (the specular term) is replaced by x^20 in five
-//     double multiplies plus a rounding certificate (spec20); a tree with a
-//     term it cannot certify (~1 evaluation in 2^24), or with a node that did
-//     not fit the pool, is flagged, and fix_kernel re-evaluates its pixel:
+//     double multiplies plus a rounding certificate (spec20, rt_spec20.h); a
+//     tree with a term it cannot certify (~1 evaluation in 2^24), or with a
+//     node that did not fit the pool, is flagged, and fix_kernel re-evaluates its pixel:
 //     node by node in heap order, each node's ray re-derived from the root
 //     (registers only, no per-lane ray queue), traced with rtm::pow_d;
 //   * the <= 64 primitives are staged per block into LDS as per-type SoA;
@@ -41,6 +41,7 @@
 #include "rt_glibc_math.h"
 #include "rt_levelq.h"
 #include "rt_prims.h"
+#include "rt_spec20.h"
 
 namespace rt {
 namespace queue {
@@ -87,28 +88,6 @@ struct Hit {
     unsigned cnt;         // tests | shadow rays << 16 (work counters)
     bool amb;             // a specular term needs the exact pow (spec20)
 };
-
-// The specular factor (float)(pow((double)dp, 20.0) * (double)pspec) of
-// :270 -- g++'s promoting std::pow, i.e. glibc's double pow -- without the
-// table-driven pow.  x^20 by repeated squaring in double is within 2^-50 of
-// x^20 (a float x squares exactly; four more roundings), and glibc's pow is
-// within 0.52 ulp of it, so the double product glibc's value gives lies
-// within 2^-49 of d = p * pspec.  If d * (1 - 2^-48) and d * (1 + 2^-48)
-// round to the same float, so does that product (rounding is monotonic):
-// that float is the reference's.  Otherwise (a float rounding boundary within
-// 2^-48 of d, about one evaluation in 2^24) `amb` is set and the caller
-// re-evaluates the node with rtm::pow_d (EXACT).  UNCERT (test hook,
-// RT_QUEUE_EXACT_ALL=1): no term is certified, every one takes that path.
-template <bool EXACT, bool UNCERT = false>
-__device__ __forceinline__ float spec20(float dp, float pspec, bool &amb)
-{
-    if (EXACT) return (float)(rtm::pow_d((double)dp, 20.0) * (double)pspec);
-    const double x = (double)dp, x2 = x * x, x4 = x2 * x2, x8 = x4 * x4, x16 = x8 * x8;
-    const double d = (x16 * x4) * (double)pspec;
-    const float lo = (float)(d * (1.0 - 0x1p-48)), hi = (float)(d * (1.0 + 0x1p-48));
-    amb |= lo != hi || UNCERT;
-    return lo;
-}
 
 // get_normal, :162-177.
 __device__ __forceinline__ v3 normal_at(const Scene &S, int p, v3 pt)

@@ -6,6 +6,10 @@
 // intersect spheres and planes with the same float operations; what differs
 // per tracer (the far distance, the initial result, the no-hit primitive) is
 // a traits struct, and everything about materials stays in the tracers.
+// Besides the tracers' frame tests, nearest_n, first_occluder, light_len_inv
+// and fill_lists are run on their own (tests/native/gpu_prims_check.hip) and
+// compared bit for bit with the references' loops at the edges where they
+// branch: tests/test_gpu_prims.py.
 #ifndef RT_PRIMS_H
 #define RT_PRIMS_H
 
@@ -83,17 +87,25 @@ __device__ __forceinline__ float plane_cand_lean(float4 g, const ray3 &r)
 // cost more exec-mask instructions than VALU:
 // profiles/r04/whitted_lean_loops_ab.log.)
 // T: static constexpr float far (the distance a hit must beat), int result0
-// (result without a hit), int miss (prim without a hit: 0x7fffffff, or a
-// negative value, which a tie then never replaces).
+// (result without a hit), int miss (prim without a hit: 0x7fffffff or a
+// negative value).  Inside, "no hit yet" is always a negative prim (`none`),
+// which `id < prim[r]` never replaces on a tie: a first candidate exactly at
+// T::far is refused, as by the references' strict '<' (with prim at
+// 0x7fffffff it was taken); a non-negative T::miss is put in at the end.
+// (For a negative T::miss the prim[r] >= 0 test says nothing more than
+// id < prim[r] does; it stays because queue.hip's kernels compile to other
+// code without it.)  Checked alone, at these edges, against the references'
+// loops by tests/test_gpu_prims.py.
 template <int R, class T>
 __device__ __forceinline__ void nearest_n(const PrimLists &S, const ray3 (&ray)[R], float (&dist)[R], int (&prim)[R],
                                           int (&result)[R])
 {
+    constexpr int none = T::miss < 0 ? T::miss : -1;
     bool bad[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
         dist[r] = T::far;
-        prim[r] = T::miss;
+        prim[r] = none;
         result[r] = T::result0;
         bad[r] = false;
     }
@@ -128,7 +140,7 @@ __device__ __forceinline__ void nearest_n(const PrimLists &S, const ray3 (&ray)[
     for (int r = 0; r < R; r++) {
         if (wave_any(bad[r])) {                         // (rare: det outside sqrt_nr's range)
             dist[r] = T::far;
-            prim[r] = T::miss;
+            prim[r] = none;
             result[r] = T::result0;
             for (int k = 0; k < S.ns; k++) {
                 int res;
@@ -152,6 +164,10 @@ __device__ __forceinline__ void nearest_n(const PrimLists &S, const ray3 (&ray)[
             prim[r] = take ? id : prim[r];
             result[r] = take ? 1 : result[r];
         }
+    }
+    if (T::miss >= 0) {
+#pragma unroll
+        for (int r = 0; r < R; r++) prim[r] = prim[r] < 0 ? T::miss : prim[r];
     }
 }
 

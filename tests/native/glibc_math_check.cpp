@@ -2,11 +2,20 @@
 // se-195-project-ray-tracer_amd/csrc/rt_glibc_math.h reproduces the host
 // glibc's float libm bit for bit over the hot path's input domains.
 // Prints one "name checked mismatches first_bad_input" line per domain.
+// Arguments: "quick" (reduced ranges), and float bit patterns (0x...) of the
+// pspec values to check rt_spec20.h's rounding certificate with: one more
+// line per pspec, "spec20_<pspec bits> checked certified_but_wrong
+// first_wrong_input uncertified uncertified_at_or_above_0x3c000000
+// [uncertified inputs, ascending, at most 256]".
 #include <math.h>
 #include <stdio.h>
 #include <stdint.h>
 #include <string.h>
+#include <stdlib.h>
+#include <algorithm>
+#include <vector>
 #include "rt_glibc_math.h"
+#include "rt_spec20.h"
 
 static inline bool same(float a, float b)
 {
@@ -77,6 +86,54 @@ int main(int argc, char **argv)
             if (rtm::d2u(rtm::pow_d(x, 20.0)) != rtm::d2u(::pow(x, 20.0))) { bad++; if (u < first) first = u; }
         }
         printf("pow_d_y20 %llu %llu 0x%08llx\n", (unsigned long long)hi, bad, first == ~0ull ? 0ull : first);
+        fflush(stdout);
+    }
+    // rt::queue::spec20<false> (queue.hip's specular factor: x^20 in five
+    // multiplies and a rounding certificate) against what it stands for,
+    // (float)(pow((double)dp, 20.0) * (double)pspec) with the host's pow, for
+    // every float dp in (0, 2]: a certified result must be that float.
+    {
+        std::vector<float> ps;
+        for (int a = 1; a < argc; a++)
+            if (!strncmp(argv[a], "0x", 2)) ps.push_back(rtm::u2f((uint32_t)strtoul(argv[a], nullptr, 16)));
+        const int np = (int)ps.size();
+        const uint32_t hi = step_hi;
+        std::vector<unsigned long long> wrong(np, 0), first(np, ~0ull), unc_hi(np, 0);
+        std::vector<std::vector<uint32_t>> unc(np);
+#pragma omp parallel
+        {
+            std::vector<unsigned long long> w(np, 0), f(np, ~0ull), uh(np, 0);
+            std::vector<std::vector<uint32_t>> un(np);
+#pragma omp for schedule(static, 1 << 16) nowait
+            for (uint64_t u = 1; u <= hi; u++) {
+                const float dp = rtm::u2f((uint32_t)u);
+                const double p = ::pow((double)dp, 20.0);
+                for (int j = 0; j < np; j++) {
+                    bool amb = false;
+                    const float fast = rt::queue::spec20<false>(dp, ps[j], amb);
+                    if (amb) {
+                        un[j].push_back((uint32_t)u);
+                        if (u >= 0x3c000000u) uh[j]++;
+                    } else if (rtm::f2u(fast) != rtm::f2u((float)(p * (double)ps[j]))) {
+                        w[j]++;
+                        if (u < f[j]) f[j] = u;
+                    }
+                }
+            }
+#pragma omp critical
+            for (int j = 0; j < np; j++) {
+                wrong[j] += w[j]; unc_hi[j] += uh[j];
+                if (f[j] < first[j]) first[j] = f[j];
+                unc[j].insert(unc[j].end(), un[j].begin(), un[j].end());
+            }
+        }
+        for (int j = 0; j < np; j++) {
+            std::sort(unc[j].begin(), unc[j].end());
+            printf("spec20_%08x %llu %llu 0x%08llx %zu %llu", rtm::f2u(ps[j]), (unsigned long long)hi, wrong[j],
+                   first[j] == ~0ull ? 0ull : first[j], unc[j].size(), unc_hi[j]);
+            for (size_t k = 0; k < unc[j].size() && k < 256; k++) printf(" 0x%08x", unc[j][k]);
+            printf("\n");
+        }
         fflush(stdout);
     }
     // The exact smallpt domain: r1 = (2*PI) * (m * 2^-23), m < 2^23.

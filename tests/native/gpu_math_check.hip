@@ -1,5 +1,6 @@
 // tests/native/gpu_math_check.hip -- device vs host-glibc check of
-// se-195-project-ray-tracer_amd/csrc/rt_glibc_math.h.  Test infrastructure:
+// se-195-project-ray-tracer_amd/csrc/rt_glibc_math.h, of rt_common.h's
+// helpers and of rt_spec20.h's rounding certificate.  Test infrastructure:
 // built into tests/native/libgpu_math_check.so by tests/native/Makefile.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -9,6 +10,8 @@
 #include <vector>
 #include "rt_glibc_math.h"
 #include "rt_common.h"
+#include "rt_spec20.h"
+#include <algorithm>
 
 __device__ __host__ inline float eval(int fn, float x)
 {
@@ -140,5 +143,142 @@ extern "C" int gmc_run_pow20(uint32_t lo, uint32_t hi, uint64_t *mismatches, uin
     (void)hipFree(d);
     *mismatches = bad;
     *first_bad = first;
+    return 0;
+}
+
+// rt::cvt_i32_x86 on the device vs the host's (int)f -- cvttss2si on x86-64,
+// what rt_common.h says it mirrors -- for all 2^32 float bit patterns,
+// compared as integers (a NaN's or an overflow's result is one fixed integer).
+__global__ void cvt_kernel(uint32_t lo, uint32_t n, int32_t *out)
+{
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        out[i] = rt::cvt_i32_x86(rtm::u2f(lo + i));
+}
+
+extern "C" int gmc_run_cvt(uint32_t lo, uint32_t hi, uint64_t *mismatches, uint32_t *first_bad)
+{
+    const uint32_t CH = 1u << 26;
+    int32_t *d = nullptr;
+    std::vector<int32_t> h(CH);
+    if (hipMalloc(&d, sizeof(int32_t) * CH) != hipSuccess) return -1;
+    uint64_t bad = 0;
+    uint32_t first = 0xffffffffu;
+    for (uint64_t base = lo; base <= hi; base += CH) {
+        const uint32_t n = (uint32_t)((hi - base + 1) < CH ? (hi - base + 1) : CH);
+        hipLaunchKernelGGL(cvt_kernel, dim3(4096), dim3(256), 0, 0, (uint32_t)base, n, d);
+        if (hipMemcpy(h.data(), d, sizeof(int32_t) * n, hipMemcpyDeviceToHost) != hipSuccess) {
+            (void)hipFree(d);
+            return -2;
+        }
+        const int T = 16;
+        std::vector<uint64_t> tb(T, 0);
+        std::vector<uint32_t> tf(T, 0xffffffffu);
+        std::vector<std::thread> th;
+        for (int t = 0; t < T; t++)
+            th.emplace_back([&, t]() {
+                for (uint32_t i = t; i < n; i += T) {
+                    volatile float x = rtm::u2f((uint32_t)base + i);
+                    const int32_t r = (int)x;
+                    if (r != h[i]) { tb[t]++; if ((uint32_t)base + i < tf[t]) tf[t] = (uint32_t)base + i; }
+                }
+            });
+        for (auto &x : th) x.join();
+        for (int t = 0; t < T; t++) { bad += tb[t]; if (tf[t] < first) first = tf[t]; }
+        if (base + CH > hi) break;
+    }
+    (void)hipFree(d);
+    *mismatches = bad;
+    *first_bad = first;
+    return 0;
+}
+
+// rt::queue::spec20's certificate on the device: for the float bit patterns
+// [lo, hi] of dp and each pspec, spec20<false> (five v_mul_f64 and the
+// +-2^-48 roundings) against spec20<true> (rtm::pow_d, pinned to glibc's pow
+// above).  Per pspec: the count of certified results that differ, the count
+// of uncertified ones (and of those at or above SPEC20_HI, below which the
+// results underflow), and up to SPEC20_CAP inputs of each.
+constexpr int SPEC20_CAP = 256, SPEC20_MAXP = 16;
+constexpr uint32_t SPEC20_HI = 0x3c000000u;
+
+struct Spec20Out {
+    unsigned long long wrong[SPEC20_MAXP], uncert[SPEC20_MAXP], uncert_hi[SPEC20_MAXP];
+    uint32_t wrong_list[SPEC20_MAXP][SPEC20_CAP], uncert_list[SPEC20_MAXP][SPEC20_CAP];
+};
+
+struct Spec20P { float v[SPEC20_MAXP]; };
+
+__global__ void spec20_kernel(uint32_t lo, uint64_t n, Spec20P ps, int np, Spec20Out *out)
+{
+    for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t u = lo + (uint32_t)i;
+        const float dp = rtm::u2f(u);
+        for (int j = 0; j < np && j < SPEC20_MAXP; j++) {
+            bool amb = false, unused = false;
+            const float fast = rt::queue::spec20<false>(dp, ps.v[j], amb);
+            const float exact = rt::queue::spec20<true>(dp, ps.v[j], unused);
+            if (amb) {
+                const unsigned long long k = atomicAdd(&out->uncert[j], 1ull);
+                if (k < (unsigned long long)SPEC20_CAP) out->uncert_list[j][k] = u;
+                if (u >= SPEC20_HI) atomicAdd(&out->uncert_hi[j], 1ull);
+            } else if (rtm::f2u(fast) != rtm::f2u(exact)) {
+                const unsigned long long k = atomicAdd(&out->wrong[j], 1ull);
+                if (k < (unsigned long long)SPEC20_CAP) out->wrong_list[j][k] = u;
+            }
+        }
+    }
+}
+
+extern "C" int gmc_spec20_cap() { return SPEC20_CAP; }
+
+// wrong / uncert / uncert_hi: np counts; wrong_list / uncert_list: np rows of
+// SPEC20_CAP inputs, the first min(count, SPEC20_CAP) of each ascending (all
+// of them when the count is within the cap).  host_uncert / host_uncert_list:
+// the same from spec20<false> run on the host.
+extern "C" int gmc_run_spec20(uint32_t lo, uint32_t hi, const float *pspec, int np, uint64_t *wrong, uint64_t *uncert,
+                              uint64_t *uncert_hi, uint32_t *wrong_list, uint32_t *uncert_list, uint64_t *host_uncert,
+                              uint32_t *host_uncert_list)
+{
+    if (np < 1 || np > SPEC20_MAXP || hi < lo) return -3;
+    Spec20P ps{};
+    for (int j = 0; j < np; j++) ps.v[j] = pspec[j];
+    Spec20Out *d = nullptr;
+    if (hipMalloc(&d, sizeof(Spec20Out)) != hipSuccess) return -1;
+    if (hipMemset(d, 0, sizeof(Spec20Out)) != hipSuccess) { (void)hipFree(d); return -1; }
+    hipLaunchKernelGGL(spec20_kernel, dim3(4096), dim3(256), 0, 0, lo, (uint64_t)hi - lo + 1, ps, np, d);
+    // the host's certificate meanwhile
+    const int T = 16;
+    std::vector<std::vector<std::vector<uint32_t>>> hl(T, std::vector<std::vector<uint32_t>>(np));
+    std::vector<std::thread> th;
+    for (int t = 0; t < T; t++)
+        th.emplace_back([&, t]() {
+            for (uint64_t u = (uint64_t)lo + t; u <= hi; u += T)
+                for (int j = 0; j < np; j++) {
+                    bool amb = false;
+                    (void)rt::queue::spec20<false>(rtm::u2f((uint32_t)u), ps.v[j], amb);
+                    if (amb) hl[t][j].push_back((uint32_t)u);
+                }
+        });
+    for (auto &x : th) x.join();
+    std::vector<Spec20Out> h(1);
+    const bool ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(h.data(), d, sizeof(Spec20Out), hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d);
+    if (!ok) return -2;
+    for (int j = 0; j < np; j++) {
+        wrong[j] = h[0].wrong[j];
+        uncert[j] = h[0].uncert[j];
+        uncert_hi[j] = h[0].uncert_hi[j];
+        const size_t nw = std::min<uint64_t>(wrong[j], SPEC20_CAP), nu = std::min<uint64_t>(uncert[j], SPEC20_CAP);
+        std::sort(h[0].wrong_list[j], h[0].wrong_list[j] + nw);
+        std::sort(h[0].uncert_list[j], h[0].uncert_list[j] + nu);
+        memcpy(wrong_list + (size_t)j * SPEC20_CAP, h[0].wrong_list[j], sizeof(uint32_t) * SPEC20_CAP);
+        memcpy(uncert_list + (size_t)j * SPEC20_CAP, h[0].uncert_list[j], sizeof(uint32_t) * SPEC20_CAP);
+        std::vector<uint32_t> all;
+        for (int t = 0; t < T; t++) all.insert(all.end(), hl[t][j].begin(), hl[t][j].end());
+        std::sort(all.begin(), all.end());
+        host_uncert[j] = all.size();
+        for (size_t k = 0; k < (size_t)SPEC20_CAP; k++) host_uncert_list[(size_t)j * SPEC20_CAP + k] = k < all.size() ? all[k] : 0u;
+    }
     return 0;
 }

@@ -81,6 +81,7 @@ def lib():
         L.orq_scene_init.argtypes = [C.POINTER(QPrimitive), C.c_int]
         L.orq_render.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                  _u64p, C.c_int]
+        L.orq_primitive_intersect.argtypes = [C.POINTER(QPrimitive), C.c_void_p, C.POINTER(C.c_float)]
         L.or_fnv1a64.argtypes = [C.c_void_p, C.c_size_t]
         L.or_fnv1a64.restype = C.c_uint64
         _lib = L

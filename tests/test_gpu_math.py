@@ -1,5 +1,7 @@
 """GPU check of rt_glibc_math.h: device powf/expf/sinf/cosf (v_fma_f64 ...)
-vs the host glibc, exhaustively over the hot path's input domains."""
+vs the host glibc, exhaustively over the hot path's input domains; of
+rt_common.h's cvt_i32_x86 for every float; and of rt_spec20.h's rounding
+certificate against rtm::pow_d on the device."""
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -17,3 +19,34 @@ def test_device_pow_d_matches_host_glibc():
     import gpu_native
     n, bad, first = gpu_native.pow20_check()
     assert n > 1.08e9 and bad == 0, (bad, first)
+
+
+def test_device_cvt_i32_x86_matches_host_conversion():
+    """(int)f as x86-64 converts it (cvttss2si: INT_MIN for NaN and overflow),
+    every one of the 2^32 float bit patterns, compared as integers."""
+    import gpu_native
+    n, bad, first = gpu_native.cvt_check()
+    assert n == 2 ** 32 and bad == 0, (bad, first)
+
+
+def test_device_spec20_certificate():
+    """The queue tracer's specular shortcut on the device (v_mul_f64,
+    v_cvt_f32_f64): for every float dp in (0, 2] and every pspec of
+    test_glibc_math.spec20_pspec(), a certified spec20<false> equals
+    spec20<true> (rtm::pow_d, pinned to glibc's pow above) bit for bit, the
+    device leaves uncertified exactly the inputs the host does, and -- so that
+    certifying nothing cannot pass -- at most 2^-20 of the dp bit patterns
+    [0x3c000000, 0x40000000], and at least one input for some pspec."""
+    import gpu_native
+    from test_glibc_math import SPEC20_MAX_UNCERTIFIED, spec20_pspec
+    res = gpu_native.spec20_check(spec20_pspec())
+    for b, r in sorted(res.items()):
+        print("spec20 pspec 0x%08x: certified-but-different %d %s, uncertified device %d %s, host %d %s"
+              % (b, r["wrong"][0], [hex(u) for u in r["wrong"][1]], r["uncertified"][0],
+                 [hex(u) for u in r["uncertified"][1]], r["host_uncertified"][0],
+                 [hex(u) for u in r["host_uncertified"][1]]))
+    for b, r in sorted(res.items()):
+        assert r["wrong"][0] == 0, (hex(b), r["wrong"])
+        assert r["uncertified"] == r["host_uncertified"], (hex(b), r)
+        assert r["uncertified_hi"] <= SPEC20_MAX_UNCERTIFIED, (hex(b), r)
+    assert any(r["uncertified"][0] > 0 for r in res.values())
