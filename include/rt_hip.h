@@ -517,6 +517,78 @@ int rtq_render(const rtq_primitive *prims, int nprims, uint32_t *pixels, int w, 
 int rtq_render_async(const rtq_primitive *d_prims, int nprims, uint32_t *d_pixels, int w, int h,
                      int row_begin, int row_end, uint64_t *d_counters, void *stream);
 
+/* ------------------------------------------------------------ level-pass tracers, ray queries */
+/* What does this ray hit, and is this point shadowed?  Caller-supplied rays
+ * against the primitives of the Whitted tracer (raytracer3.0.06) or of the
+ * queue tracer (Raytracer3.2.03), with the nearest-hit and shadow loops their
+ * frames are rendered with.
+ *
+ * A prepared scene holds at most 64 primitives (the references allocate 50).
+ * The creators take a HOST array and return when the scene is ready; the
+ * array is free again then.  *_prims_set_async replaces the whole primitive
+ * array from DEVICE memory (as rtw_render_async / rtq_render_async take it):
+ * nprims may change, and so may which primitives are lights or occluders.
+ * rtp_scene_destroy waits for the device; NULL is a no-op.
+ *
+ * d_rays: device memory, 6 floats per ray (o.xyz, d.xyz), used as given: the
+ * direction is NOT normalised.  Any float may stand anywhere: the answers are
+ * whatever the reference's own loop yields for those floats, NaN and
+ * infinities included.  The outputs are device memory, one element per ray,
+ * and must not alias the inputs.
+ *
+ * NEAREST: the reference's nearest-hit loop -- Whitted: raytracer.cpp:39-49
+ * over Primitive_Intersect (scene.cpp:125-190), far = 1e6f; queue tracer:
+ * raytracer_non_OpenCL.c:181-193, far = 1e7f -- i.e. the smallest distance
+ * strictly below far, ties to the lowest primitive index:
+ *   d_id[r]      the primitive index, or -1 on a miss;
+ *   d_t[r]       the distance, bit for bit, or on a miss the tracer's far;
+ *   d_result[r]  1 for a hit from outside (HIT), -1 for a hit from inside a
+ *                sphere (INPRIM), 0 for a miss -- for both tracers (the queue
+ *                reference's own variable would still hold its initial 1).
+ * Each of the three is nullable; at least one must be given.  d_tmax
+ * (nullable, one float per ray): a hit is reported only when its distance is
+ * < d_tmax[r], strictly; far still applies (the bound is min(tmax, far)), and
+ * a NaN bound accepts nothing.  That is what the reference's loop started at
+ * the bound returns: a candidate's distance does not depend on the distance
+ * to beat.
+ *
+ * SHADOW / OCCLUDER: the references' shadow loop (raytracer.cpp:76-110,
+ * raytracer_non_OpenCL.c:224-241).  The occluders -- Whitted: the primitives
+ * with m_Light == 0; queue tracer: those with !is_light -- are visited in
+ * index order, each tested with the distance to beat set to d_tmax[r]
+ * (required; no far applies):
+ *   SHADOW    d_id[r] = 1 if any occluder is nearer than d_tmax[r], else 0;
+ *   OCCLUDER  d_id[r] = the primitive index where the reference's loop
+ *             breaks (the first such occluder in index order), or -1.
+ * Both require d_id and never write d_t or d_result.
+ *
+ * Every call is asynchronous on `stream`, allocates nothing, never
+ * synchronises and keeps no per-launch state, so any number of calls may be
+ * captured into graphs.  A query enqueued after a *_prims_set_async on the
+ * same stream sees the new primitives (other streams need the caller's own
+ * ordering, as for any buffer); a captured set reads d_prims at every replay.
+ * nrays == 0 is RT_OK and launches nothing.  RT_ERR_INVALID, with nothing
+ * launched: a null scene, d_rays, prims or out; an unknown kind; no output the
+ * kind writes; a missing d_tmax where required; nrays above INT32_MAX; nprims
+ * outside 1..64; a set through the other tracer's entry point; a create while
+ * the library's stream is capturing; another current device than the scene's.
+ * The checks that need no device come first.
+ * RT_PRIMS_QUERY_BLOCKS=<n> (read at the call) caps the grid and
+ * RT_PRIMS_QUERY_RAYS=1|2 picks NEAREST's rays per lane, for tests and tools:
+ * the same bits either way. */
+typedef struct rtp_scene rtp_scene;
+int rtw_prims_create(const rt_primitive *prims, int nprims, rtp_scene **out);
+int rtq_prims_create(const rtq_primitive *prims, int nprims, rtp_scene **out);
+int rtp_scene_destroy(rtp_scene *scene);
+int rtw_prims_set_async(rtp_scene *scene, const rt_primitive *d_prims, int nprims, void *stream);
+int rtq_prims_set_async(rtp_scene *scene, const rtq_primitive *d_prims, int nprims, void *stream);
+
+#define RTP_QUERY_NEAREST  0  /* the nearest hit */
+#define RTP_QUERY_SHADOW   1  /* shadowed or not */
+#define RTP_QUERY_OCCLUDER 2  /* the shadow loop's exit: the first occluder in index order */
+int rtp_query_async(const rtp_scene *scene, const float *d_rays, const float *d_tmax, size_t nrays, int kind,
+                    float *d_t, int *d_id, int *d_result, void *stream);
+
 /* Host helper: AllocateBuffers' seed fill (smallptGPU.cpp:105-110) --
  * srand(seed); seeds[i] = max(rand(), 2) for i < n, with the host libc's
  * rand() (glibc on the reference's Linux build). */

@@ -15,6 +15,10 @@ what the tests, bench.py and __graft_entry__ drive.
                (spt_scene_render_async / _groups_async / _list_async)
     Queue    : queue_render()  ~ raytracer_non_kernel
                (Raytracer3.2.03/.../raytracer_non_OpenCL.c:285-449) on the GPU
+    Queries  : SmallptScene.query() / .radiance() on a prepared smallpt scene;
+               PrimScene.query() on the Whitted or the queue tracer's
+               primitives (rtp_query_async): nearest hit, shadowed or not,
+               the first occluder
 """
 import ctypes as C
 
@@ -24,13 +28,15 @@ from . import ppm, scenes
 from .device import SmallptDeviceFrame
 from ._lib import (Camera, Float4, Primitive, QPrimitive, RTError, Sphere, Vec3, check, device_count, entry, lib,
                    set_device, SPT_COST_MAX, SPT_COUNT_RAYS, SPT_LIST_SET, SPT_DIRECT_LIGHTING, SPT_PATH_TRACING,
-                   SPT_QUERY_ANY, SPT_QUERY_NEAREST, SPT_QUERY_OCCLUDER)
+                   SPT_QUERY_ANY, SPT_QUERY_NEAREST, SPT_QUERY_OCCLUDER, RTP_QUERY_NEAREST, RTP_QUERY_SHADOW,
+                   RTP_QUERY_OCCLUDER)
 
 __all__ = ["Camera", "Primitive", "QPrimitive", "Float4", "Sphere", "Vec3", "RTError", "scenes", "lib", "check",
            "device_count", "set_device", "whitted_render", "queue_render", "SmallptFrame", "SmallptScene",
-           "SmallptMulti", "SmallptDeviceFrame",
+           "SmallptMulti", "SmallptDeviceFrame", "PrimScene",
            "SPT_PATH_TRACING", "SPT_DIRECT_LIGHTING", "SPT_COUNT_RAYS", "SPT_COST_MAX", "SPT_LIST_SET",
-           "SPT_QUERY_NEAREST", "SPT_QUERY_ANY", "SPT_QUERY_OCCLUDER"]
+           "SPT_QUERY_NEAREST", "SPT_QUERY_ANY", "SPT_QUERY_OCCLUDER",
+           "RTP_QUERY_NEAREST", "RTP_QUERY_SHADOW", "RTP_QUERY_OCCLUDER"]
 
 
 def whitted_render(w, h, row_begin=20, row_end=None, prims=None, nprims=None, frame=None,
@@ -290,6 +296,114 @@ class SmallptScene:
     def close(self):
         if self.handle:
             lib().spt_scene_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PrimScene:
+    """The Whitted or the queue tracer's primitives prepared for ray queries
+    (rtw_prims_create / rtq_prims_create): `prims` is a host array of
+    Primitive (tracer="whitted") or QPrimitive (tracer="queue"), 1..64 of
+    them.  .handle is passed to rtp_query_async.  Freed with close() / garbage
+    collection."""
+
+    TRACERS = {"whitted": ("rtw_prims_create", "rtw_prims_set_async", Primitive),
+               "queue": ("rtq_prims_create", "rtq_prims_set_async", QPrimitive)}
+    # query kinds by name (include/rt_hip.h RTP_QUERY_*)
+    QUERY_KINDS = {"nearest": RTP_QUERY_NEAREST, "shadow": RTP_QUERY_SHADOW, "occluder": RTP_QUERY_OCCLUDER}
+    FAR = {"whitted": 1000000.0, "queue": 10000000.0}      # d_t of a miss
+
+    def __init__(self, prims, nprims, tracer="whitted"):
+        if tracer not in self.TRACERS:
+            raise ValueError("PrimScene: tracer %r is not one of %s" % (tracer, sorted(self.TRACERS)))
+        self.tracer, self.n = tracer, nprims
+        self.handle = C.c_void_p()
+        ptr = None if prims is None else C.cast(prims, C.c_void_p)
+        check(entry(self.TRACERS[tracer][0])(ptr, nprims, C.byref(self.handle)))
+
+    def set(self, d_prims, nprims, stream=None):
+        """Replaces the whole primitive array (rtw_ / rtq_prims_set_async) from
+        DEVICE memory: `d_prims` is a contiguous torch device tensor of any
+        dtype holding at least nprims 96-byte primitives (a uint8 tensor made
+        from the ctypes array's bytes, say), or a raw device address (an int).
+        nprims may differ from the scene's.  Asynchronous on `stream` (a torch
+        stream or a raw handle; default: torch's current stream where torch is
+        loaded, else the null stream): queries enqueued after it on that
+        stream see the new primitives.  The tensor must stay alive until the
+        stream has passed the call."""
+        size = C.sizeof(self.TRACERS[self.tracer][2])
+        if hasattr(d_prims, "data_ptr"):
+            if not (d_prims.is_cuda and d_prims.is_contiguous()
+                    and d_prims.numel() * d_prims.element_size() >= size * max(int(nprims), 0)):
+                raise ValueError("set: d_prims must be a contiguous device tensor of at least %d x nprims bytes" % size)
+            dev, d_prims = d_prims.device, d_prims.data_ptr()
+        else:
+            dev = None
+        if stream is None:
+            import sys
+            torch = sys.modules.get("torch")
+            stream = torch.cuda.current_stream(dev) if torch is not None and torch.cuda.is_initialized() else None
+        stream = getattr(stream, "cuda_stream", stream)
+        check(entry(self.TRACERS[self.tracer][1])(self.handle, d_prims, nprims, stream))
+        self.n = nprims
+
+    def query(self, rays, tmax=None, kind="nearest", out=None, stream=None):
+        """What the rays hit (rtp_query_async): `rays` is a contiguous float32
+        device tensor [n, 6] (o.xyz, d.xyz; the direction is used as given),
+        `tmax` a float32 device tensor [n] -- required for "shadow" and
+        "occluder" (the distance an occluder must be nearer than), the
+        optional bound of "nearest" (a hit must be strictly nearer).  Returns
+        (t, id, result): "nearest" the distance (float32; FAR[tracer] on a
+        miss), the primitive index or -1, and 1 (hit from outside), -1 (from
+        inside a sphere) or 0 (miss); "shadow" (None, 1 or 0, None);
+        "occluder" (None, the first occluder's index in primitive order or -1,
+        None); id and result are int32.  out=(t, id, result) takes the
+        caller's tensors: for "nearest" any may be None, which leaves that
+        output out (not all three); the shadow kinds use id only.
+        Asynchronous on `stream` (a torch stream or a raw handle; default:
+        torch's current stream); allocates only the outputs it was not given."""
+        import torch
+        if kind not in self.QUERY_KINDS:
+            raise ValueError("query: kind %r is not one of %s" % (kind, sorted(self.QUERY_KINDS)))
+        if not (rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 6
+                and rays.is_contiguous()):
+            raise ValueError("query: rays must be a contiguous float32 device tensor [n, 6]")
+        n = rays.shape[0]
+        if tmax is not None and not (tmax.is_cuda and tmax.dtype == torch.float32 and tmax.numel() == n
+                                     and tmax.is_contiguous()):
+            raise ValueError("query: tmax must be a contiguous float32 device tensor [n]")
+        nearest = kind == "nearest"
+        if not nearest and tmax is None:
+            raise ValueError("query: kind %r needs tmax" % kind)
+        if out is None:
+            t = torch.empty(n, dtype=torch.float32, device=rays.device) if nearest else None
+            ids = torch.empty(n, dtype=torch.int32, device=rays.device)
+            res = torch.empty(n, dtype=torch.int32, device=rays.device) if nearest else None
+        else:
+            t, ids, res = out
+            t, res = (t, res) if nearest else (None, None)
+            for x, dt in ((t, torch.float32), (ids, torch.int32), (res, torch.int32)):
+                if x is not None and not (x.is_cuda and x.dtype == dt and x.numel() == n and x.is_contiguous()):
+                    raise ValueError("query: out must hold contiguous device tensors [n]: float32, int32, int32")
+            if ids is None and (not nearest or (t is None and res is None)):
+                raise ValueError("query: out holds no tensor that kind %r writes" % kind)
+        if stream is None:
+            stream = torch.cuda.current_stream(rays.device)
+        stream = getattr(stream, "cuda_stream", stream)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        if n:                                                  # (an empty tensor has no address to pass)
+            check(entry("rtp_query_async")(self.handle, rays.data_ptr(), ptr(tmax), n, self.QUERY_KINDS[kind],
+                                           ptr(t), ptr(ids), ptr(res), stream))
+        return t, ids, res
+
+    def close(self):
+        if self.handle:
+            lib().rtp_scene_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __del__(self):

@@ -17,6 +17,7 @@ SPT_COUNT_RAYS = 0x100
 SPT_COST_MAX = 0x200
 SPT_LIST_SET = 0x800
 SPT_QUERY_NEAREST, SPT_QUERY_ANY, SPT_QUERY_OCCLUDER = 0, 1, 2
+RTP_QUERY_NEAREST, RTP_QUERY_SHADOW, RTP_QUERY_OCCLUDER = 0, 1, 2
 
 # Every symbol include/rt_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = ("rt_last_error", "rt_device_count", "rt_set_device", "rt_release", "rt_cached_bytes",
@@ -30,7 +31,9 @@ EXPORTS = ("rt_last_error", "rt_device_count", "rt_set_device", "rt_release", "r
            "spt_multi_create", "spt_multi_destroy", "spt_multi_set_scene", "spt_multi_bands", "spt_multi_upload",
            "spt_multi_render_async", "spt_multi_gather_async", "spt_multi_sync", "spt_multi_download",
            "spt_multi_read_frame", "spt_multi_counters", "spt_multi_band_buffers", "spt_render_multi",
-           "spt_multi_cache_info", "rtq_render", "rtq_render_async")
+           "spt_multi_cache_info", "rtq_render", "rtq_render_async",
+           "rtw_prims_create", "rtq_prims_create", "rtp_scene_destroy", "rtw_prims_set_async", "rtq_prims_set_async",
+           "rtp_query_async")
 
 
 class RTError(RuntimeError):
@@ -151,6 +154,13 @@ def lib():
     if hasattr(L, "rtq_render"):
         L.rtq_render.argtypes = [vp, i, vp, i, i, u64p]
         L.rtq_render_async.argtypes = [vp, i, vp, i, i, i, i, u64p, vp]
+    if hasattr(L, "rtp_query_async"):
+        L.rtw_prims_create.argtypes = [vp, i, C.POINTER(vp)]
+        L.rtq_prims_create.argtypes = [vp, i, C.POINTER(vp)]
+        L.rtp_scene_destroy.argtypes = [vp]
+        L.rtw_prims_set_async.argtypes = [vp, vp, i, vp]
+        L.rtq_prims_set_async.argtypes = [vp, vp, i, vp]
+        L.rtp_query_async.argtypes = [vp, vp, vp, C.c_size_t, i, vp, vp, vp, vp]
     _lib = L
     return L
 
