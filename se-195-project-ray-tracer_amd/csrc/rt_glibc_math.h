@@ -292,6 +292,80 @@ RTM_HD void sincosf(float x, float &sn, float &cs)
     if (abstop < 0x398) { sn = x; cs = 1.0f; }
 }
 
+// sinf and cosf of phi = 2.f * PI_F * u for a GetRandom draw u = m * 2^-23,
+// 0 <= m < 2^23: glibc's bits, as sincosf(phi) above, on exactly those 2^23
+// arguments (tests/test_sincos_draw.py goes through all of them on the host
+// against the libm and against sincosf; tests/test_gpu_sincos_draw.py on the
+// device).  What the general form spends on arguments that never come is left
+// out:
+//  * quadrant: reduce_fast's n = round(phi * 2/pi) equals (m + 2^20) >> 21 for
+//    every m -- an integer add and a shift in place of an f64 multiply, a
+//    conversion, an add and a shift.  (A float rint(phi * 2/pi)
+//    is wrong for two m.)  n runs from 0 to 4; the selects and signs below
+//    use bits of the same integer t = m + 2^20: n & 1 is bit 21, n & 2 bit 22;
+//  * signs on the results: sg only ever multiplies xr, rounding is sign-
+//    symmetric, so sine(xs) = sg * sine(xr).  Together with the negated cosine
+//    of n & 2 the two signs are sin < 0 for n in {2, 3} (bit 22 of t) and
+//    cos < 0 for n in {1, 2} (bit 22 of t + 2^21): an XOR on each float;
+//  * no tiny path: m = 0 is the only draw with |phi| < 2^-12, and the
+//    polynomials give +0 and 1.0f there;
+//  * Horner form of the same two polynomials: it rounds to the same floats on
+//    this domain (not on all of |x| < 120: sincosf keeps glibc's order), with
+//    two f64 multiplies where glibc's order has six.
+// mbits: any word whose low 23 bits are m -- the bits of u + 1.0f, or of the
+// [2, 4) float that the draw was made from (smallpt.hip get_random_f), which
+// costs the caller nothing.  Callers: smallpt.hip pass B (r1) and pass A (phi;
+// a lane without a draw passes u = 0), spt_radiance.h rad_sample_lights (phi)
+// and rad_diffuse (r1); each argument is 2.f * PI_F times a get_random value
+// and nothing else.
+//
+// fma_dc: a * b + c for a constant c.  The device compiler puts a constant
+// addend into the two-address v_fmac_f64's destination: a register pair that
+// holds the constant for the whole kernel and a copy in front of every use
+// (ten more VGPRs for the five Horner addends below, which cost several
+// variants of render_kernel a wave of occupancy or a spill).  v_fma_f64 reads
+// the addend from scalar registers instead: one instruction, no vector
+// register.  c must be a compile-time constant: the "s" operand of a value
+// that differs between lanes would be the first active lane's.
+RTM_HD double fma_dc(double a, double b, double c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    double d;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(c));
+    return d;
+#else
+    return fma_d(a, b, c);
+#endif
+}
+
+RTM_HD void sincos_2pi_draw_bits(uint32_t mbits, float u, float &sn, float &cs)
+{
+    const float phi = (2.f * 3.14159265358979323846f) * u;     // the callers' 2.f * PI_F * u
+    const uint32_t t = (mbits & 0x007fffffu) + 0x00100000u;
+    const uint32_t n = t >> 21;
+    const double xr = fma_d(-(double)n, 0x1.921fb54442d18p+0, (double)phi);
+    const double s = xr * xr;
+    double p = fma_d(s, -0x1.994eb3774cf24p-13, 0x1.1107605230bc4p-7);
+    p = fma_dc(s, p, -0x1.555545995a603p-3);
+    const float ps = (float)fma_d(s * xr, p, xr);
+    double c = fma_d(s, 0x1.99343027bf8c3p-16, -0x1.6c087e89a359dp-10);
+    c = fma_dc(s, c, 0x1.55553e1068f19p-5);
+    c = fma_dc(s, c, -0x1.ffffffd0c621cp-2);
+    const float pc = (float)fma_d(s, c, 1.0);
+    const bool odd = (t & 0x00200000u) != 0;
+    const uint32_t sn_sign = (t << 9) & 0x80000000u;
+    const uint32_t cs_sign = ((t + 0x00200000u) << 9) & 0x80000000u;
+    sn = u2f(f2u(odd ? pc : ps) ^ sn_sign);
+    cs = u2f(f2u(odd ? ps : pc) ^ cs_sign);
+}
+
+// The same from the draw alone (precondition: u = m * 2^-23, 0 <= m < 2^23;
+// u + 1.0f is then exact and its mantissa is m).
+RTM_HD void sincos_2pi_draw(float u, float &sn, float &cs)
+{
+    sincos_2pi_draw_bits(f2u(u + 1.0f), u, sn, cs);
+}
+
 // glibc 2.35 double pow (e_pow.c), as its FMA build (__pow_fma, selected on
 // every x86-64 host with FMA/AVX2) evaluates it: every fma_d below is one
 // vfmadd/vfmsub of that build, every other op a plain IEEE double op, in its

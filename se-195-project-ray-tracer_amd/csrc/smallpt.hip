@@ -834,14 +834,22 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                                    cmx.z * kcx + cmy.z * kcy + cmd.z);
                 const v3 vn = vnorm(need_bounce ? cu : rdir);
                 if (need_bounce) {
-                    const float r1 = 2.f * PI_F * x1;
                     const float r2s = sqrt_exact(x2);
                     const v3 v = vxcross(wv, vn);
-                    float sn1, cs1;
-                    rtm::sincosf(r1, sn1, cs1);
+                    // sinf / cosf of r1 = 2 PI x1 and sqrtf(1 - x2).  draw_trig: the
+                    // quadrant from f1's mantissa; 1 - x2 lies in [2^-23, 1] for every
+                    // draw, inside sqrt_nr's range (x2 itself can be 0: r2s keeps the guard)
+                    float sn1, cs1, r2c;
+                    if constexpr (V.draw_trig()) {
+                        rtm::sincos_2pi_draw_bits(__float_as_uint(f1), x1, sn1, cs1);
+                        r2c = sqrt_nr(1 - x2);
+                    } else {
+                        rtm::sincosf(2.f * PI_F * x1, sn1, cs1);
+                        r2c = sqrt_exact(1 - x2);
+                    }
                     const v3 u = vsmul(cs1 * r2s, vn);
                     v3 nd = vadd(u, vsmul(sn1 * r2s, v));
-                    nd = vadd(nd, vsmul(sqrt_exact(1 - x2), wv));
+                    nd = vadd(nd, vsmul(r2c, wv));
                     ray.d = nd;                          // origin: hit
                 } else {
                     v3 rorig = vsmul(0.1f, rdir);
@@ -1106,15 +1114,18 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                     const float ddn = inv_sign * dp;
                     const float cos2t = 1.f - nnt * nnt * (1.f - ddn * ddn);
                     const bool tir = cos2t < 0.f;
-                    float x1 = 0.f, x2 = 0.f;
-                    if (a_L || (with_r && !tir)) x1 = get_random(s0, s1);   // L: u2; R: the roulette draw
+                    // (g1: the [2, 4) float x1 is made from, whose mantissa gives
+                    // the angle's quadrant; no draw: 2, x1 = 0)
+                    float g1 = 2.f, x2 = 0.f;
+                    if (a_L || (with_r && !tir)) g1 = get_random_f(s0, s1);   // L: u2; R: the roulette draw
+                    const float x1 = __builtin_fmaf(g1, .5f, -1.f);
                     if (a_L) x2 = get_random(s0, s1);           // L: u1
                     const float zz = 1.f - 2.f * x2;            // UniformSampleSphere, :61-69
                     const float q = 1.f - zz * zz;
                     const float sq = sqrt_exact((!with_r || a_L) ? ((0.f > q) ? 0.f : q) : (tir ? 1.f : cos2t));
-                    const float phi = 2.f * PI_F * x1;
-                    float sp_sin, sp_cos;
-                    rtm::sincosf(phi, sp_sin, sp_cos);
+                    float sp_sin, sp_cos;                       // of phi = 2 PI x1 (no draw: x1 = 0)
+                    if constexpr (V.draw_trig()) rtm::sincos_2pi_draw_bits(__float_as_uint(g1), x1, sp_sin, sp_cos);
+                    else rtm::sincosf(2.f * PI_F * x1, sp_sin, sp_cos);
                     const v3 unit = mk(sq * sp_cos, sq * sp_sin, zz);
                     v3 sp = vsmul(lc.w, unit);
                     sp = vadd(sp, mk(lg.x, lg.y, lg.z));

@@ -63,6 +63,14 @@ struct Variant {
     // RAYS one's loop; their one-ray query runs only in iterations without a
     // shadow ray
     SPT_HD constexpr bool key_accept() const { return park() && !(geo == GEO_GLOBAL && dual && cmode != CNT_NONE); }
+    // pass A's and pass B's angles go through rtm::sincos_2pi_draw and pass B's
+    // sqrt(1 - x2) through sqrt_nr without its range guard (both exact on a
+    // draw's 2^23 values); else: rtm::sincosf and sqrt_exact -- the hierarchy
+    // kernels, which sit at their register bounds (6 and 4 waves per SIMD)
+    // and answer the shorter forms with more scratch, a lost wave (the RAYS
+    // binary kernels, 95 -> 99 VGPRs) or up to 25 more v_readlane inside
+    // their loops (profiles/r17/sincos_draw_resource_usage.txt)
+    SPT_HD constexpr bool draw_trig() const { return park(); }
     SPT_HD constexpr bool persist() const { return geo == GEO_WIDE; }              // waves fetch tiles from a work counter
     SPT_HD constexpr bool sched() const { return geo == GEO_BVH || geo == GEO_WIDE; }   // group order / cost code
     SPT_HD constexpr bool gstore() const { return geo == GEO_BVH; }                // stores staged per tile group

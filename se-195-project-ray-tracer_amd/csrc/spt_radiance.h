@@ -7,7 +7,7 @@
 // the sphere loop (query_bf) and the walks (bvh_walk, wide_walk) are
 // render_kernel's own; the shading below is a restatement of geomfunc.h in the
 // reference's order, one small function per step, with render_kernel's exact
-// primitives (get_random, sqrt_exact, rcp_nr, rtm::sincosf, vnorm).
+// primitives (get_random, sqrt_exact, rcp_nr, rtm::sincos_2pi_draw, vnorm).
 #ifndef SPT_RADIANCE_H
 #define SPT_RADIANCE_H
 
@@ -182,9 +182,8 @@ __device__ __forceinline__ bool rad_sample_lights(const Scene &S, RadPath &P, ui
         const float zz = 1.f - 2.f * u1;                        // :61-69
         const float q = 1.f - zz * zz;
         const float r = sqrt_exact((0.f > q) ? 0.f : q);
-        const float phi = 2.f * PI_F * u2;
-        float sn, cs;
-        rtm::sincosf(phi, sn, cs);
+        float sn, cs;                                           // of phi = 2 PI u2
+        rtm::sincos_2pi_draw(u2, sn, cs);
         const v3 unit = mk(r * cs, r * sn, zz);
         v3 sp = vsmul(lc.w, unit);
         sp = vadd(sp, mk(lg.x, lg.y, lg.z));
@@ -216,7 +215,7 @@ __device__ __forceinline__ bool rad_diffuse(RadPath &P, uint32_t &s0, uint32_t &
 {
     P.rad = vadd(P.rad, vmul(P.thr, P.lsum));
     if (DL) return true;
-    const float r1 = 2.f * PI_F * get_random(s0, s1);
+    const float u1 = get_random(s0, s1);                        // r1 = 2 PI u1
     const float r2 = get_random(s0, s1);
     if (P.depth > 6) return true;                               // :184 (the draws are taken before it)
     const float r2s = sqrt_exact(r2);
@@ -226,11 +225,11 @@ __device__ __forceinline__ bool rad_diffuse(RadPath &P, uint32_t &s0, uint32_t &
     u = vnorm(u);
     v3 v = vxcross(w, u);
     float sn, cs;
-    rtm::sincosf(r1, sn, cs);
+    rtm::sincos_2pi_draw(u1, sn, cs);
     u = vsmul(cs * r2s, u);
     v = vsmul(sn * r2s, v);
     v3 newDir = vadd(u, v);
-    newDir = vadd(newDir, vsmul(sqrt_exact(1 - r2), w));
+    newDir = vadd(newDir, vsmul(sqrt_nr(1 - r2), w));          // 1 - r2 in [2^-23, 1]: sqrt_nr's range
     P.ray.d = newDir;                                           // origin: the hit point
     return false;
 }

@@ -55,6 +55,9 @@ def main():
     asm, kern = sys.argv[1], sys.argv[2]
     srcdir = sys.argv[3] if len(sys.argv) > 3 else "se-195-project-ray-tracer_amd/csrc"
     (lstart, lend), phases, ops = ranges(srcdir + "/" + SRC)
+    hdr = open(srcdir + "/rt_glibc_math.h").read().split("\n")
+    trig = (next(i + 1 for i, l in enumerate(hdr) if "struct sincos_poly" in l) - 1,
+            next(i + 1 for i, l in enumerate(hdr) if l.startswith("// glibc 2.35 double pow (e_pow.c)")))
     lines = open(asm).read().split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^\w*%s\w*:" % re.escape(kern), l))
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
@@ -82,7 +85,9 @@ def main():
             if f == "rt_glibc_math.h":
                 if n <= 40:                      # (bit-cast / fma helpers: the caller decides)
                     continue
-                kind = "sincosf" if n >= 183 else "powf (toInt)"
+                # sincosf: everything from the sincos table to pow_d -- sincosf itself and
+                # sincos_2pi_draw / sincos_2pi_draw_bits / fma_dc, which stand in for it
+                kind = "sincosf" if trig[0] <= n < trig[1] else "powf (toInt)"
                 break
             if f == "rt_common.h":
                 kind = {True: "sqrt_nr / rsq"}.get(True)
