@@ -29,6 +29,7 @@
 #include "spt_policy.h"
 #include "spt_layout.h"
 #include "spt_accept.h"
+#include "spt_rng.h"
 
 namespace rt {
 namespace smallpt {
@@ -49,12 +50,10 @@ struct SphereGeo { float4 g; };          // centre.xyz, rad*rad (same float prod
 // c = -1 that is (f - 2) / 2 and for c = -1.5 it is (f - 2) / 2 - .5f, exact
 // (f / 2 - 1 and f / 2 - 1.5 are representable, as are the reference's two
 // steps each), in one op instead of two or three.
+// (the two stream updates: spt_rng.h, two VALU each)
 __device__ __forceinline__ float get_random_f(uint32_t &s0, uint32_t &s1)
 {
-    s0 = 36969u * (s0 & 65535u) + (s0 >> 16);
-    s1 = 18000u * (s1 & 65535u) + (s1 >> 16);
-    const uint32_t ires = (s0 << 16) + s1;
-    return __uint_as_float((ires & 0x007fffffu) | 0x40000000u);
+    return __uint_as_float(sptrng::draw<true>(s0, s1));
 }
 __device__ __forceinline__ float get_random(uint32_t &s0, uint32_t &s1)
 {
@@ -345,7 +344,11 @@ struct Counts { unsigned isect, isectp, samples; unsigned long long tests; };
 // product build.
 #ifdef RT_SPT_PROF
 enum { PB_ITER, PB_SHADOW, PB_NEAREST, PB_DIFF, PB_SPEC, PB_REFR, PB_LIGHT, PB_BOUNCE, PB_DONE,
-       PB_WCALL, PB_WSTEP, PB_WLEAF, PB_WSHADE, PB_FLUSH, PB_N };
+       PB_WCALL, PB_WSTEP, PB_WLEAF, PB_WSHADE, PB_FLUSH,
+       // flush passes by what started them (the first that holds, in this order):
+       // the threshold, a DIFF hit with no free slot, a sample ending behind a
+       // parked one, an emitter term behind an unresolved entry, the drain
+       PB_FL_THRESH, PB_FL_SLOT, PB_FL_ENDS, PB_FL_EMIT, PB_FL_DRAIN, PB_N };
 __device__ unsigned long long g_spt_prof[2 * PB_N];
 #define SPT_PROF(b)                                                                        \
     do {                                                                                   \
@@ -926,6 +929,17 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                     const float maxt = rg[6 * SQ_RING + e];
                     const bool have = lane < m;
                     SPT_PROF_ONLY(if (have) prof_l[PB_FLUSH]++; if (lane == 0) prof_w[PB_FLUSH]++;)
+                    SPT_PROF_ONLY({
+                        const int why = sptpolicy::sq_flush(q_count, q_T)        ? PB_FL_THRESH
+                                        : wave_any(f_diff && npend == 2)         ? PB_FL_SLOT
+                                        : wave_any(f_ends && npark > 0)          ? PB_FL_ENDS
+                                        : wave_any(f_emit && npend > npark)      ? PB_FL_EMIT
+                                                                                 : PB_FL_DRAIN;
+                        _Pragma("unroll") for (int b = PB_FL_THRESH; b <= PB_FL_DRAIN; b++) {
+                            if (have && b == why) prof_l[b]++;
+                            if (lane == 0 && b == why) prof_w[b]++;
+                        }
+                    })
                     const bool occ = shadow_bf(geo, rs, maxt, have);
                     const unsigned long long unocc = __builtin_amdgcn_ballot_w64(have && !occ);
                     // owners, oldest entry first (:154-161, then :229-230).  (The
@@ -2471,7 +2485,7 @@ extern "C" int spt_pack_pixels_async(const float *d_colors, uint32_t *d_pixels, 
 }
 
 #ifdef RT_SPT_PROF
-// Tools-only: reads and clears the block profile (18 counters).
+// Tools-only: reads and clears the block profile (2 * PB_N counters).
 extern "C" int spt_prof_read(unsigned long long *out)
 {
     hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(rt::smallpt::g_spt_prof), sizeof(rt::smallpt::g_spt_prof));

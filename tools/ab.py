@@ -52,8 +52,11 @@ def child():
     ts = _spt.event_ms(run, 0, int(os.environ.get("REPS", "5")), st)
     if os.environ.get("PROF"):      # block counters of a tools-only instrumented build
         names = ["iter", "shadow", "nearest", "diff", "spec", "refr", "light", "bounce", "done",
-                 "wcall", "wstep", "wleaf", "wshade", "flush"]   # flush: ring entries popped / passes
-        buf = (C.c_ulonglong * (2 * len(names)))()
+                 "wcall", "wstep", "wleaf", "wshade", "flush",   # flush: ring entries popped / passes
+                 # ... and the same by what started the pass: threshold, no free slot,
+                 # previous sample unfolded, emitter term, drain
+                 "fl_thr", "fl_slot", "fl_ends", "fl_emit", "fl_drain"]
+        buf = (C.c_ulonglong * (2 * max(len(names), 64)))()   # (room for a build with more counters than names)
         L.spt_prof_read(buf)
         for b, nm in enumerate(names):
             lanes, waves = buf[2 * b], buf[2 * b + 1]
