@@ -426,6 +426,59 @@ int spt_scene_radiance_async(const spt_scene *scene, const float *d_rays, size_t
                              float *d_radiance, int first_sample, int nsamples, int mode,
                              void *stream);
 
+/* ------------------------------------------------------------ smallpt, pixel lists */
+/* Samples where the caller wants them: a list of pixels, each with its own
+ * sample count, rendered into the frame buffers of the other entry points.
+ *
+ * d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h: the frame, as for
+ * spt_scene_render_async (colours and seeds at slot (h-y-1)*w+x, d_pixels at
+ * y*w+x; the two seed buffers may be one).  w * h must fit an int32.
+ * d_list: device memory, nlist pixel indices p = y*w+x, the index d_pixels
+ * uses.  An entry outside [0, w*h) is skipped, so -1 padding is legal.  The
+ * caller guarantees that d_list is a set: no per-call check is made, and a
+ * pixel listed twice is traced by two lanes that race on one RNG chain and
+ * one accumulator -- results are then undefined (the SPT_LIST_SET promise,
+ * which this entry point always takes).
+ * d_take: nullable, device memory, nlist counts: the samples to add to entry
+ * e's pixel; a negative count is taken as 0.  NULL: every entry takes
+ * nsamples.  With d_take, nsamples must be 0.
+ * d_done: nullable, device memory, w*h int32 at the colour slot: a fourth
+ * plane of the accumulator holding the pixel's currentSample.  Given, a
+ * pixel's samples are numbered d_done[slot] + j and d_done[slot] += take is
+ * written back; first_sample must then be 0.  NULL: they are numbered
+ * first_sample + j, as everywhere else.
+ * mode: SPT_PATH_TRACING or SPT_DIRECT_LIGHTING, without flag bits.
+ *
+ * Per listed pixel with take t: (s0, s1) is read from d_seeds_in and, when
+ * the first sample's number is > 0, the running average from d_colors; then
+ * for j = 0 .. t-1 the two jitter values are drawn, the camera ray is built
+ * exactly as UpdateRenderingCPU builds it (smallptCPU.cpp:84-105),
+ * RadiancePathTracing or RadianceDirectLighting runs, and the result is
+ * folded as smallptCPU.cpp:110-118 folds it; after the last sample the colour,
+ * the advanced seeds (to d_seeds_out) and d_pixels[p] (the toInt pack) are
+ * written.  An entry with t == 0 copies its two seed words to d_seeds_out and
+ * writes nothing else.  Pixels that are not listed are not touched in any
+ * buffer, d_seeds_out included.  Per pixel the result is what any other
+ * window computes for that sample range, bit for bit, whichever kernel family
+ * the scene runs: "pixel p after n samples" does not depend on what the
+ * other pixels were given.
+ *
+ * Asynchronous on `stream`; allocates nothing, never synchronises, takes no
+ * work-counter entry and keeps no per-launch state, so any number of calls
+ * may be captured into graphs; learns no dispatch order.  Ordered after
+ * earlier spt_scene_update_async calls on the same stream.  nlist == 0 is
+ * RT_OK and launches nothing.  RT_ERR_INVALID: a null scene, camera, d_colors,
+ * d_seeds_in, d_seeds_out, d_pixels or d_list; w or h < 1 (or w * h above
+ * INT32_MAX); a negative nsamples or first_sample; d_take together with
+ * nsamples > 0; d_done together with first_sample > 0; an unknown mode or one
+ * carrying flag bits; nlist above INT32_MAX; another current device.
+ * RT_SPT_QUERY_BLOCKS=<n> (read at the call) caps the grid, for tests. */
+int spt_scene_render_pixels_async(const spt_scene *scene, const rt_camera *camera,
+                                  float *d_colors, const uint32_t *d_seeds_in, uint32_t *d_seeds_out,
+                                  uint32_t *d_pixels, int w, int h,
+                                  const int32_t *d_list, const int32_t *d_take, size_t nlist, int nsamples,
+                                  int32_t *d_done, int first_sample, int mode, void *stream);
+
 /* ------------------------------------------------------------ smallpt, several GPUs */
 /* One frame tiled over the GPUs of a node in row bands:
  * band k owns the k-th contiguous chunk of the flipped colour / seed slots,

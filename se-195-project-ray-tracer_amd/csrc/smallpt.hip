@@ -1514,6 +1514,10 @@ __global__ void __launch_bounds__(256) list_dedup_kernel(const int *__restrict__
 // caller's rays, one path per lane over the same loops and walks.
 #include "spt_radiance.h"
 
+// Pixel lists (spt_scene_render_pixels_async): the camera's rays through the
+// same estimator for the pixels the caller lists, a sample count per entry.
+#include "spt_pixels.h"
+
 }  // namespace smallpt
 }  // namespace rt
 
@@ -2216,6 +2220,68 @@ extern "C" int spt_scene_radiance_async(const spt_scene *sc, const float *d_rays
                                                  : pick_radiance<GEO_GLOBAL>(dl);
     hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * wpb), lds, (hipStream_t)stream, a, sc->bvh);
     return rtrt::check_launch("spt radiance_kernel");
+}
+
+// ---- pixel lists (spt_pixels.h)
+namespace {
+using PixelsKernel = decltype(&rt::smallpt::pixels_kernel<0, false>);
+
+template <int GEO>
+PixelsKernel pick_pixels(bool dl)
+{
+    return dl ? rt::smallpt::pixels_kernel<GEO, true> : rt::smallpt::pixels_kernel<GEO, false>;
+}
+}  // namespace
+
+extern "C" int spt_scene_render_pixels_async(const spt_scene *sc, const rt_camera *camera, float *d_colors,
+                                             const uint32_t *d_seeds_in, uint32_t *d_seeds_out, uint32_t *d_pixels,
+                                             int w, int h, const int32_t *d_list, const int32_t *d_take, size_t nlist,
+                                             int nsamples, int32_t *d_done, int first_sample, int mode, void *stream)
+{
+    if (!sc || !camera || !d_colors || !d_seeds_in || !d_seeds_out || !d_pixels || !d_list)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: null scene, camera, colours, seeds, pixels or list");
+    if (w < 1 || h < 1 || (long long)w * h > (long long)INT32_MAX)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: bad frame size");
+    if (nsamples < 0 || first_sample < 0)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: negative nsamples or first_sample");
+    if (d_take && nsamples > 0)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: nsamples must be 0 beside d_take");
+    if (d_done && first_sample > 0)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: first_sample must be 0 beside d_done");
+    if (mode != SPT_PATH_TRACING && mode != SPT_DIRECT_LIGHTING)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: unknown mode (no flags are taken)");
+    if (nlist > (size_t)INT32_MAX) return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: list too long");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != sc->device)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: the scene's device is not the current one");
+    if (nlist == 0) return RT_OK;
+    // spt_scene_radiance_async's family, LDS bytes and grid: persistent
+    // blocks over the list's chunks; RT_SPT_QUERY_BLOCKS caps the grid.
+    const SceneSizes sizes{sc->n, sc->nlights, sc->bvh.wnodes, sc->bvh.wdepth};
+    int geo = scene_geo(*sc);
+    if (geo == GEO_LDS && radiance_lds_bytes(geo, sizes) > (size_t)CU_LDS_BYTES) geo = GEO_GLOBAL;
+    const size_t lds = radiance_lds_bytes(geo, sizes);
+    const int wpb = query_wpb(geo);
+    constexpr int PIXELS_BLOCKS_PER_CU = 8;
+    const long long nchunks = ((long long)nlist + 63) / 64;
+    long long nblocks = std::min<long long>((nchunks + wpb - 1) / wpb,
+                                            (long long)sc->cus * (geo == GEO_WIDE ? 1 : PIXELS_BLOCKS_PER_CU));
+    if (const char *cap = getenv("RT_SPT_QUERY_BLOCKS")) nblocks = std::min<long long>(nblocks, std::max(atoi(cap), 1));
+    // RT_SPT_PIXELS_REFILL=0 (read at the call; tools/pixel_list_time.py): lanes
+    // claim only when their whole wave is out of samples.  Same results.
+    const char *rf = getenv("RT_SPT_PIXELS_REFILL");
+    const int refill = !(rf && !strcmp(rf, "0"));
+    const int opts = sptpolicy::pack_split(0, false, 0, 255, sptpolicy::SptTune().batch, 0);
+    const rt::smallpt::PixelsArgs a{*camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h, d_list, d_take,
+                                    (int)nlist, nsamples, d_done, first_sample, sc->n, sc->nlights, sc->d_soa, opts,
+                                    refill};
+    const bool dl = mode == SPT_DIRECT_LIGHTING;
+    const PixelsKernel kern = geo == GEO_WIDE  ? pick_pixels<GEO_WIDE>(dl)
+                              : geo == GEO_BVH ? pick_pixels<GEO_BVH>(dl)
+                              : geo == GEO_LDS ? pick_pixels<GEO_LDS>(dl)
+                                               : pick_pixels<GEO_GLOBAL>(dl);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * wpb), lds, (hipStream_t)stream, a, sc->bvh);
+    return rtrt::check_launch("spt pixels_kernel");
 }
 
 namespace {

@@ -27,7 +27,7 @@ EXPORTS = ("rt_last_error", "rt_device_count", "rt_set_device", "rt_release", "r
            "spt_group_count", "spt_scene_render_list_async", "spt_groups_pack_async", "spt_groups_unpack_async",
            "spt_pack_pixels_async",
            "spt_scene_update_async", "spt_scene_update_info", "spt_scene_read_hierarchy", "spt_multi_update_scene",
-           "spt_scene_query_async", "spt_scene_radiance_async",
+           "spt_scene_query_async", "spt_scene_radiance_async", "spt_scene_render_pixels_async",
            "spt_multi_create", "spt_multi_destroy", "spt_multi_set_scene", "spt_multi_bands", "spt_multi_upload",
            "spt_multi_render_async", "spt_multi_gather_async", "spt_multi_sync", "spt_multi_download",
            "spt_multi_read_frame", "spt_multi_counters", "spt_multi_band_buffers", "spt_render_multi",
@@ -133,6 +133,8 @@ def lib():
         L.spt_scene_query_async.argtypes = [vp, vp, vp, C.c_size_t, i, vp, vp, vp]
     if hasattr(L, "spt_scene_radiance_async"):
         L.spt_scene_radiance_async.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, i, i, i, vp]
+    if hasattr(L, "spt_scene_render_pixels_async"):
+        L.spt_scene_render_pixels_async.argtypes = [vp, vp, vp, vp, vp, vp, i, i, vp, vp, C.c_size_t, i, vp, i, i, vp]
     if hasattr(L, "spt_multi_create"):
         ip = C.POINTER(C.c_int)
         L.spt_multi_create.argtypes = [vp, u, i, i, vp, i, C.POINTER(vp)]

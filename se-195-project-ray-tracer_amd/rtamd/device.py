@@ -1,8 +1,9 @@
 """SmallptDeviceFrame: one prepared smallpt scene plus device-resident frame
 buffers, launched asynchronously -- the path the GPU tests and the tools
 drive.  This module is the one place in the package that spells out the calls
-to spt_scene_render_async, spt_scene_render_groups_async and
-spt_scene_render_list_async (include/rt_hip.h).
+to spt_scene_render_async, spt_scene_render_groups_async,
+spt_scene_render_list_async and spt_scene_render_pixels_async
+(include/rt_hip.h).
 
 torch is imported inside the functions, so `import rtamd` works without it.
 """
@@ -36,6 +37,17 @@ class SmallptDeviceFrame:
         self.colors = torch.zeros(3 * w * h, dtype=torch.float32, device=self.device)
         self.pixels = torch.zeros(w * h, dtype=torch.int32, device=self.device)
         self.counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self._done = None
+
+    @property
+    def done(self):
+        """The samples every pixel has had (its currentSample), int32 [w * h]
+        in slot order (h - y - 1) * w + x like `colors`; made, zeroed, at its
+        first use (render_pixels(use_done=True))."""
+        if self._done is None:
+            import torch
+            self._done = torch.zeros(self.w * self.h, dtype=torch.int32, device=self.device)
+        return self._done
 
     @property
     def groups_total(self):
@@ -101,13 +113,88 @@ class SmallptDeviceFrame:
                 nsamples, mode, d_counters, stream)
         return _check(rc) if check else rc
 
+    def render_pixels(self, pixels, take=None, nsamples=0, *, use_done=True, first_sample=0, mode=SPT_PATH_TRACING,
+                      seeds_in=None, stream=None, check=True):
+        """One asynchronous launch (spt_scene_render_pixels_async) that adds
+        samples to the listed pixels only: `pixels` is a contiguous int32
+        device tensor of indices y * w + x (the index of `self.pixels`; an
+        entry outside the frame, -1 say, is skipped; no pixel may repeat),
+        `take` a contiguous int32 device tensor of as many sample counts, or
+        None: every entry takes `nsamples`.  use_done=True numbers a pixel's
+        samples from self.done and adds its take there, so successive calls
+        continue every pixel where it stands; use_done=False numbers them from
+        first_sample, as render() does.  seeds_in defaults to self.seeds with
+        use_done (a progressive loop: start it with
+        frame.seeds.copy_(frame.seeds0)), else to seeds0, as for render().
+        Unlisted pixels are not touched in any buffer.  Returns the entry
+        point's code (raises RTError on failure unless check=False).
+        Allocates nothing on the device (but self.done at its first use) and
+        never synchronises."""
+        import torch
+
+        def is_list(x):
+            return x.is_cuda and x.dtype == torch.int32 and x.dim() == 1 and x.is_contiguous()
+        if not is_list(pixels):
+            raise ValueError("render_pixels: pixels must be a contiguous int32 device tensor [n]")
+        if take is not None and not (is_list(take) and take.numel() == pixels.numel()):
+            raise ValueError("render_pixels: take must be a contiguous int32 device tensor as long as pixels")
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        if seeds_in is None:
+            seeds_in = self.seeds if use_done else self.seeds0
+        # the locals below carry the header's parameter names, in its order
+        scene = self.scene.handle
+        camera = C.byref(self.camera)
+        d_colors = self.colors.data_ptr()
+        d_seeds_in = seeds_in.data_ptr()
+        d_seeds_out = self.seeds.data_ptr()
+        d_pixels = self.pixels.data_ptr()
+        w, h = self.w, self.h
+        nlist = pixels.numel()
+        d_list = pixels.data_ptr() if nlist else self.pixels.data_ptr()   # (an empty tensor has no address to pass)
+        d_take = None if take is None else (take.data_ptr() if nlist else self.pixels.data_ptr())
+        d_done = self.done.data_ptr() if use_done else None
+        stream = getattr(stream, "cuda_stream", stream)
+        rc = entry("spt_scene_render_pixels_async")(
+            scene, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h, d_list, d_take, nlist, nsamples,
+            d_done, first_sample, mode, stream)
+        return _check(rc) if check else rc
+
+    def budget_list(self, budget, order="tile"):
+        """(pixels, take) for render_pixels from an h x w integer budget map
+        (torch or numpy; budget[y, x] = the samples to add to the pixel
+        `self.pixels` holds at y * w + x): the non-zero entries only, in 8 x 8
+        tile order (tiles row by row, a tile's pixels row by row), so that
+        neighbouring pixels share a wave -- or, order="row", by pixel index,
+        64 pixels of one row to a wave: a wave's paths are less alike, its
+        share of the frame is spread wider ("Pixel lists": the
+        faster order on a 10k-sphere scene).  Two int32 device tensors.
+        Waits for the device (it counts the entries)."""
+        if order not in ("tile", "row"):
+            raise ValueError("budget_list: order is 'tile' or 'row'")
+        import torch
+        b = torch.as_tensor(np.asarray(budget) if not torch.is_tensor(budget) else budget).to(self.device)
+        if tuple(b.shape) != (self.h, self.w) or b.dtype.is_floating_point or b.dtype == torch.bool:
+            raise ValueError("budget_list: budget must be an integer map [h, w] = [%d, %d]" % (self.h, self.w))
+        if bool((b < 0).any()):
+            raise ValueError("budget_list: negative budget")
+        y, x = torch.nonzero(b, as_tuple=True)
+        tiles_x = (self.w + 7) // 8
+        if order == "tile":                                 # (nonzero's own order is the row order)
+            key = ((y >> 3) * tiles_x + (x >> 3)) * 64 + (y & 7) * 8 + (x & 7)
+            rank = torch.argsort(key)
+            y, x = y[rank], x[rank]
+        return (y * self.w + x).to(torch.int32).contiguous(), b[y, x].to(torch.int32).contiguous()
+
     def reset(self, colors=0.0, pixels=0, seeds=0):
         """Refills the output tensors in place (pixels and seeds take a 32-bit
-        pattern) and zeroes the counters."""
+        pattern) and zeroes the counters (and `done`, where it exists)."""
         self.colors.fill_(colors)
         self.pixels.fill_(_i32(pixels))
         self.seeds.fill_(_i32(seeds))
         self.counters.zero_()
+        if self._done is not None:
+            self._done.zero_()
         return self
 
     def host(self):
