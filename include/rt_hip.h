@@ -184,7 +184,17 @@ int spt_render_async(const rt_sphere *d_spheres, unsigned nspheres, const rt_cam
 
 /* Prepared scene: uploads the sphere array once (device SoA of geometry,
  * materials and per-light records; for >= 256 spheres also the exact-culling
- * sphere hierarchy).  Reuse it across frames. */
+ * sphere hierarchy).  Reuse it across frames.
+ *
+ * Sphere fields may be any floats; no scene is rejected for its values.  As
+ * in the reference (geomfunc.h:32-59) the radius counts only through rad *
+ * rad -- a sphere of radius -2 is the sphere of radius 2 -- and a sphere whose
+ * radius or centre is not finite is never hit.  A hierarchy scene keeps both
+ * rules: boxes are taken from |rad|, and a sphere whose float box c -+ |rad|
+ * is not finite widens no box, so its frames and query answers are the full
+ * scan's, bit for bit.  A NaN accumulator (an infinite emitter channel times
+ * a zero throughput) packs as the reference's x86-64 build packs it: the
+ * float-to-int conversion gives INT_MIN. */
 typedef struct spt_scene spt_scene;
 int spt_scene_create(const rt_sphere *spheres, unsigned nspheres, spt_scene **out);
 int spt_scene_destroy(spt_scene *scene);
@@ -199,7 +209,8 @@ int spt_scene_destroy(spt_scene *scene);
  *       kernel where its block -- scene copy and per-wave areas, [16] -- would
  *       exceed a compute unit's LDS: the same bits either way.)
  *   [1] spheres   [2] lights (emitters)
- *   [3] spheres tested outside the hierarchy (radius > 64 x the median, <= 16)
+ *   [3] spheres tested outside the hierarchy (|radius| > 64 x the median
+ *       |radius|, NaN radii apart; <= 16)
  *   [4] binary hierarchy nodes   [5] 8-wide nodes   [6] 8-wide levels
  *   [7] the 8-wide tree's leaf size, 8, 12 or 16 (0: no 8-wide tree)
  *   [8] 1 if no sphere takes the refraction branch
@@ -241,7 +252,10 @@ int spt_scene_release_captures(const spt_scene *scene);
 
 /* Replaces spheres [first, first + count) of a prepared scene with
  * spheres[0 .. count) (host memory) in place; the sphere count stays.  Any
- * field may change.  The caller may change or free `spheres` as soon as the
+ * field may change, to any float (spt_scene_create's contract: the radius
+ * counts through rad * rad, a non-finite sphere is never hit; the refit takes
+ * boxes from |rad| and leaves a sphere whose float box is not finite out of
+ * every box).  The caller may change or free `spheres` as soon as the
  * call returns (it is copied into page-locked staging the scene keeps).
  * Device work is ordered on `stream` and nothing is synchronised: launches on
  * `stream` enqueued before the call render the old scene, launches enqueued

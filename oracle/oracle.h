@@ -101,6 +101,11 @@ void ors_render(const or_sphere *s, unsigned n, const or_camera *cam,
                 float *colors, uint32_t *seeds, uint32_t *pixels, int w, int h,
                 int row_begin, int row_end, int first_sample, int nsamples,
                 int direct_lighting, uint64_t *counters, int nthreads);
+/* The pixel pack of smallptCPU.cpp:120-122 alone, over a whole w x h
+ * accumulator: pixels[y * w + x] from colors slot (h - y - 1) * w + x, toInt
+ * per channel as the reference's x86-64 build computes it (a NaN or
+ * out-of-range float converts to INT_MIN; the shifts wrap in 32 bits). */
+void ors_pack(const float *colors, uint32_t *pixels, int w, int h);
 
 /* scene_build_complex.pl logic (HyperSphere) with the given max depth;
  * writes up to cap spheres in the Perl script's emission order, returns the

@@ -10,6 +10,7 @@
  * libm calls are the float overloads the C++ reference resolves to
  * (sqrtf, sinf/cosf, fabsf, powf).
  */
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -247,10 +248,31 @@ static Vec radiance(const or_sphere *S, unsigned n, Ray ray, uint32_t *s0, uint3
     }
 }
 
-/* toInt, vec.h:62 */
+/* toInt, vec.h:62.  The conversion as the reference's x86-64 build performs
+ * it (cvttss2si): truncation, and INT_MIN for a NaN or a value outside
+ * [-2^31, 2^31) -- undefined in C, so spelt out.  A NaN accumulator (an inf
+ * emitter channel times a zero throughput) passes the clamp and powf. */
 static int to_int(float x)
 {
-    return (int)(powf(OCLAMP(x, 0.f, 1.f), 1.f / 2.2f) * 255.f + .5f);
+    const float v = powf(OCLAMP(x, 0.f, 1.f), 1.f / 2.2f) * 255.f + .5f;
+    return (v >= -2147483648.f && v < 2147483648.f) ? (int)v : INT_MIN;
+}
+
+/* A pixel, smallptCPU.cpp:120-122: toInt(r) | toInt(g) << 8 | toInt(b) << 16,
+ * the shifts on uint32_t (what x86 computes for a shifted INT_MIN, which C
+ * leaves undefined). */
+static uint32_t pack_rgb(float r, float g, float b)
+{
+    return (uint32_t)to_int(r) | ((uint32_t)to_int(g) << 8) | ((uint32_t)to_int(b) << 16);
+}
+
+void ors_pack(const float *colors, uint32_t *pixels, int width, int height)
+{
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++) {
+            const float *col = &colors[3 * ((size_t)(height - y - 1) * width + x)];
+            pixels[(size_t)y * width + x] = pack_rgb(col[0], col[1], col[2]);
+        }
 }
 
 void ors_render(const or_sphere *S, unsigned n, const or_camera *cam, float *colors,
@@ -298,8 +320,7 @@ void ors_render(const or_sphere *S, unsigned n, const or_camera *cam, float *col
                 c.samples++;
             }
             if (nsamples > 0)                                   /* :120-122 */
-                pixels[(size_t)y * width + x] = (uint32_t)(to_int(col->x) | (to_int(col->y) << 8) |
-                                                           (to_int(col->z) << 16));
+                pixels[(size_t)y * width + x] = pack_rgb(col->x, col->y, col->z);
         }
         t_isect += c.isect; t_isectp += c.isectp; t_tests += c.tests; t_samples += c.samples;
     }

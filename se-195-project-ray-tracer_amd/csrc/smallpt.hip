@@ -375,15 +375,17 @@ __device__ int g_spt_only_group = -1;
 #endif
 
 // toInt, vec.h:62 (clamp macro keeps -0.0; glibc powf via rt_glibc_math.h).
+// A NaN accumulator (an inf emitter channel times a zero throughput) passes
+// the clamp and powf: the reference's x86 conversion makes it INT_MIN.
 __device__ __forceinline__ int to_int(float x)
 {
     const float c = (x < 0.f) ? 0.f : ((x > 1.f) ? 1.f : x);
-    return (int)(rtm::powf(c, 1.f / 2.2f) * 255.f + .5f);
+    return rt::cvt_i32_x86(rtm::powf(c, 1.f / 2.2f) * 255.f + .5f);
 }
-// A pixel, smallptCPU.cpp:120-122.
+// A pixel, smallptCPU.cpp:120-122 (the shifts in 32 bits, as x86 shifts INT_MIN).
 __device__ __forceinline__ uint32_t pack_rgb(float r, float g, float b)
 {
-    return (uint32_t)(to_int(r) | (to_int(g) << 8) | (to_int(b) << 16));
+    return (uint32_t)to_int(r) | ((uint32_t)to_int(g) << 8) | ((uint32_t)to_int(b) << 16);
 }
 
 // DUAL (path tracing, full-scan geometry, scenes with exactly one light): a
@@ -1453,8 +1455,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const float *__restrict__ col
     for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
         const int y = row_begin + (int)(p / w), x = (int)(p % w);
         const size_t i = (size_t)(h - y - 1) * w + x;
-        pixels[(size_t)y * w + x] =
-            (uint32_t)(to_int(colors[3 * i]) | (to_int(colors[3 * i + 1]) << 8) | (to_int(colors[3 * i + 2]) << 16));
+        pixels[(size_t)y * w + x] = pack_rgb(colors[3 * i], colors[3 * i + 1], colors[3 * i + 2]);
     }
 }
 

@@ -19,6 +19,7 @@
 #ifndef SPT_BVH_H
 #define SPT_BVH_H
 
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -34,7 +35,8 @@ struct f4 { float x, y, z, w; };
 constexpr float ALPHA_R = 1.f / 64.f;   // margin per unit of a box's half diagonal (spt_walk.h)
 constexpr int LEAF = 4;                  // spheres per leaf
 constexpr int MIN_SPHERES = 256;         // scenes below this are scanned in full
-constexpr int MAX_ALWAYS = 16;           // spheres tested outside the hierarchy (radius > 64 x median)
+constexpr int MAX_ALWAYS = 16;           // spheres tested outside the hierarchy (|radius| > 64 x median)
+constexpr float BOX_EMPTY_LO = 1e30f, BOX_EMPTY_HI = -1e30f;   // the empty box every min / max starts from
 #ifndef SPT_SAH_BINS
 #define SPT_SAH_BINS 64   // binned-SAH bins per axis (16: configs[4] heavy-tile rays visit ~20 % more nodes)
 #endif
@@ -53,11 +55,35 @@ struct BvhBuild {
     std::vector<int> idx;
     std::vector<HostNode> nodes;
 
-    void box(int i, float *lo, float *hi) const
+    // The float box c -+ |rad| of sphere i (the reference uses a radius only as
+    // rad * rad, geomfunc.h:42: its sign does not count).  A box with a
+    // non-finite component belongs to a sphere no ray can hit (rad * rad or
+    // |p - o|^2 is inf or NaN, and SphereIntersect's tests then all fail): it
+    // is returned as the empty box, which no min / max below notices, so such
+    // a sphere widens no node.  False for an empty box.
+    bool box(int i, float *lo, float *hi) const
     {
         const rt_sphere &q = sp[i];
         const float c[3] = {q.p.x, q.p.y, q.p.z};
-        for (int k = 0; k < 3; k++) { lo[k] = c[k] - q.rad; hi[k] = c[k] + q.rad; }
+        const float r = fabsf(q.rad);
+        bool finite = true;
+        for (int k = 0; k < 3; k++) {
+            lo[k] = c[k] - r;
+            hi[k] = c[k] + r;
+            finite = finite && fabsf(lo[k]) <= FLT_MAX && fabsf(hi[k]) <= FLT_MAX;
+        }
+        if (!finite)
+            for (int k = 0; k < 3; k++) { lo[k] = BOX_EMPTY_LO; hi[k] = BOX_EMPTY_HI; }
+        return finite;
+    }
+    // The centroid bin of a centre along an axis of extent ext from c0: the
+    // float expression truncated and clamped to [0, NB - 1]; a NaN (a NaN
+    // centre, inf / inf) goes to bin 0 without a conversion.
+    static int bin(float c, float c0, float ext, int nb)
+    {
+        const float f = (c - c0) / ext * nb;
+        if (!(f >= 0.f)) return 0;
+        return f >= (float)nb ? nb - 1 : (int)f;
     }
     float centre(int i, int k) const { return k == 0 ? sp[i].p.x : (k == 1 ? sp[i].p.y : sp[i].p.z); }
     static float area(const float *lo, const float *hi)
@@ -75,7 +101,7 @@ struct BvhBuild {
         for (int k = 0; k < 3; k++) { nd.lo[k] = 1e30f; nd.hi[k] = -1e30f; }
         for (int j = lo; j < hi; j++) {
             float a[3], b[3];
-            box(idx[j], a, b);
+            if (!box(idx[j], a, b)) continue;     // never hit: neither in the box nor in the centroid bounds
             for (int k = 0; k < 3; k++) {
                 nd.lo[k] = std::min(nd.lo[k], a[k]);
                 nd.hi[k] = std::max(nd.hi[k], b[k]);
@@ -110,8 +136,7 @@ struct BvhBuild {
             for (int q = 0; q < NB; q++)
                 for (int k = 0; k < 3; k++) { blo[q][k] = 1e30f; bhi[q][k] = -1e30f; }
             for (int j = lo; j < hi; j++) {
-                int q = (int)((centre(idx[j], ax) - clo[ax]) / ext * NB);
-                q = std::min(std::max(q, 0), NB - 1);
+                const int q = bin(centre(idx[j], ax), clo[ax], ext, NB);
                 float a[3], b[3];
                 box(idx[j], a, b);
                 cnt[q]++;
@@ -142,9 +167,7 @@ struct BvhBuild {
             const int ax = best_ax;
             const float ext = chi[ax] - clo[ax];
             auto it = std::partition(idx.begin() + lo, idx.begin() + hi, [&](int i) {
-                int q = (int)((centre(i, ax) - clo[ax]) / ext * NB);
-                q = std::min(std::max(q, 0), NB - 1);
-                return q < best_b;
+                return bin(centre(i, ax), clo[ax], ext, NB) < best_b;
             });
             mid = (int)(it - idx.begin());
             nd.axis = ax;
@@ -199,18 +222,29 @@ struct BvhBuild {
     }
 };
 
-// Splits a scene into the "always" spheres (radius > 64 x the median: the
-// ground of configs[4]) and the rest, and builds the binary tree over the rest.
+// Splits a scene into the "always" spheres (|radius| > 64 x the median
+// |radius|: the ground of configs[4]) and the rest, and builds the binary tree
+// over the rest.  The median is taken over the radii that are not NaN (a NaN
+// has no place in an order); a NaN radius is never above it.  Either side of
+// the partition is exact: the rule costs speed only.
 inline void partition_and_build(const rt_sphere *spheres, int n, std::vector<int> &always, BvhBuild &b)
 {
-    std::vector<float> rads(n);
-    for (int i = 0; i < n; i++) rads[i] = spheres[i].rad;
-    std::nth_element(rads.begin(), rads.begin() + n / 2, rads.end());
-    const float med = rads[n / 2];
+    std::vector<float> rads;
+    rads.reserve(n);
+    for (int i = 0; i < n; i++) {
+        const float r = fabsf(spheres[i].rad);
+        if (r == r) rads.push_back(r);
+    }
+    float med = 0.f;
+    if (!rads.empty()) {
+        const size_t m = rads.size() / 2;
+        std::nth_element(rads.begin(), rads.begin() + m, rads.end());
+        med = rads[m];
+    }
     std::vector<int> rest;
     always.clear();
     for (int i = 0; i < n; i++) {
-        if (spheres[i].rad > 64.f * med && (int)always.size() < MAX_ALWAYS) always.push_back(i);
+        if (fabsf(spheres[i].rad) > 64.f * med && (int)always.size() < MAX_ALWAYS) always.push_back(i);
         else rest.push_back(i);
     }
     b.sp = spheres;

@@ -93,11 +93,21 @@ SPT_RF_HD float rf_max(float a, float b)
     return a < b ? b : a;
 }
 
-// BvhBuild::box: the float box of a sphere.
+constexpr float BOX_EMPTY_LO = sptbvh::BOX_EMPTY_LO, BOX_EMPTY_HI = sptbvh::BOX_EMPTY_HI;   // the builders' empty box
+
+// BvhBuild::box: the float box c -+ |rad| of a sphere, or the empty box where
+// a component of it is not finite (such a sphere is never hit).  No entry box
+// holds an inf or a NaN, so the reductions below see ordered values alone and
+// give the same bits in any order.
 SPT_RF_HD void sphere_box(float rad, float px, float py, float pz, float *lo, float *hi)
 {
-    lo[0] = px - rad; lo[1] = py - rad; lo[2] = pz - rad;
-    hi[0] = px + rad; hi[1] = py + rad; hi[2] = pz + rad;
+    const float r = fabsf(rad);
+    lo[0] = px - r; lo[1] = py - r; lo[2] = pz - r;
+    hi[0] = px + r; hi[1] = py + r; hi[2] = pz + r;
+    bool finite = true;
+    for (int k = 0; k < 3; k++) finite = finite && fabsf(lo[k]) <= 3.402823466e+38f && fabsf(hi[k]) <= 3.402823466e+38f;
+    if (!finite)
+        for (int k = 0; k < 3; k++) { lo[k] = BOX_EMPTY_LO; hi[k] = BOX_EMPTY_HI; }
 }
 
 // The margin term ALPHA_R * R + BETA of a node box (spt_bvh.h, BvhBuild::build).
@@ -191,8 +201,6 @@ SPT_RF_HD uint32_t quantise(float v, float lo, int e, bool high)
     if (q > 255.0) q = 255.0;
     return (uint32_t)q;
 }
-
-constexpr float BOX_EMPTY_LO = 1e30f, BOX_EMPTY_HI = -1e30f;   // the builders' empty box
 
 // ------------------------------------------------------------------ topology
 constexpr int SMALL_MAX = 16;      // entries of a binary node refitted by 8 lanes

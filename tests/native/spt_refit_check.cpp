@@ -7,12 +7,14 @@
 // (geomfunc.h:71-110) ray by ray.  tests/test_refit.py builds this file into a
 // shared library with g++ -O2 -std=c++17 -ffp-contract=off -pthread; with
 // -DSPT_REFIT_MAIN it is a stand-alone program (its own scenes and edits) for
-// a run under -fsanitize=address,undefined.
+// a run under -fsanitize=address,undefined,float-cast-overflow
+// (tests/test_degenerate.py).
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <cmath>
 #include <thread>
 #include <vector>
 #include "spt_bvh.h"
@@ -120,9 +122,15 @@ long long check(const State *S, char *msg, int cap)
         for (int j = m.range[2 * i]; j < m.range[2 * i + 1]; j++) {
             const rt_sphere &q = S->sp[S->ids[j]];
             const float c[3] = {q.p.x, q.p.y, q.p.z};
+            // The float box c -+ |rad| (the reference uses rad only as rad *
+            // rad).  Exempt only where a component of that box is not finite:
+            // such a sphere is never hit (rad * rad or |p - o|^2 is inf or NaN).
+            const float r = fabsf(q.rad);
+            bool finite = true;
+            for (int k = 0; k < 3; k++) finite = finite && std::isfinite(c[k] - r) && std::isfinite(c[k] + r);
+            if (!finite) continue;
             for (int k = 0; k < 3; k++) {
-                // the float box of BvhBuild::box, as every builder takes it
-                if (!((long double)o[k] <= (long double)(c[k] - q.rad) && (long double)o[4 + k] >= (long double)(c[k] + q.rad)))
+                if (!((long double)o[k] <= (long double)(c[k] - r) && (long double)o[4 + k] >= (long double)(c[k] + r)))
                     fail("a binary node's box does not contain a sphere of its range", i, j);
             }
         }
@@ -148,7 +156,9 @@ long long check(const State *S, char *msg, int cap)
     for (int w = 0; w < S->wn; w++) {
         const uint32_t *ww = &S->words[(size_t)w * sptbvh::WIDE_WORDS];
         const int *slot = &m.wslot[8 * (size_t)w];
-        long double lo[3] = {1e30L, 1e30L, 1e30L}, hi[3] = {-1e30L, -1e30L, -1e30L};
+        // (the float constants: a node whose children are all empty holds them exactly)
+        const long double elo = sptbvh::BOX_EMPTY_LO, ehi = sptbvh::BOX_EMPTY_HI;
+        long double lo[3] = {elo, elo, elo}, hi[3] = {ehi, ehi, ehi};
         for (int s = 0; s < 8; s++) {
             if (slot[s] < 0) continue;
             const float *o = &S->nbox[8 * (size_t)slot[s]];
@@ -292,12 +302,14 @@ bool walk_binary(const State *S, const float *o, const float *d, bool shadow, fl
         const float c[3] = {a[0] - o[0], a[1] - o[1], a[2] - o[2]};
         const float dist = sqrtf(fmaf(c[0], c[0], fmaf(c[1], c[1], c[2] * c[2])));
         const float m = fmaf(r.alpha, dist, b[3]);
-        float tn = -INFINITY, tf = INFINITY;
+        float lo3[3], hi3[3];
         for (int k = 0; k < 3; k++) {
             const float tc = c[k] * r.inv[k], h = (b[k] + m) * fabsf(r.inv[k]);
-            tn = fmaxf(tn, tc - h);
-            tf = fminf(tf, tc + h);
+            lo3[k] = tc - h;
+            hi3[k] = tc + h;
         }
+        // folded as the device folds them (three NaN slabs give a NaN, which fails the test below)
+        const float tn = fmaxf(fmaxf(lo3[0], lo3[1]), lo3[2]), tf = fminf(fminf(hi3[0], hi3[1]), hi3[2]);
         const bool cross = tn <= tf && tf >= 0.f && tn <= lim;
         if (link < 0) {
             if (cross) {
@@ -406,7 +418,9 @@ long long rfc_walk(const void *s, const float *rays, const float *maxt, long lon
 #ifdef SPT_REFIT_MAIN
 // Stand-alone run: two scenes of its own (a small and a larger cloud over a
 // ground sphere), the five kinds of edit of tests/test_refit.py, each followed
-// by the containment check and both walks.
+// by the containment check and both walks; then the degenerate kinds of
+// tests/scenes_layouts.py (negative, zero and non-finite radii and centres):
+// a tree built from each, a tree refitted to each and back, both walks.
 namespace {
 uint64_t g_rng = 0x9E3779B97F4A7C15ull;
 double uni()
@@ -470,11 +484,83 @@ int run(int n, float half)
     }
     return rc;
 }
+
+// Kind k on every seventh sphere from 20 on (k == 10: every sphere from 4 on
+// with a negated radius; 11: with a NaN centre; 12: kinds 0..9 in turn).
+void degenerate(std::vector<rt_sphere> &v, int kind)
+{
+    const int n = (int)v.size();
+    auto one = [&](rt_sphere &q, int k, int j) {
+        float *c = j % 3 == 0 ? &q.p.x : (j % 3 == 1 ? &q.p.y : &q.p.z);
+        switch (k) {
+        case 0: q.rad *= -4.f; break;
+        case 1: q.rad = 0.f; break;
+        case 2: q.rad = 1e-40f; break;
+        case 3: q.rad = INFINITY; break;
+        case 4: q.rad = -INFINITY; break;
+        case 5: q.rad = NAN; break;
+        case 6: *c = NAN; break;
+        case 7: *c = j % 2 ? -INFINITY : INFINITY; break;
+        case 8: *c = j % 4 < 2 ? 3.4e38f : -3.4e38f; break;
+        case 9: *c = 3.4e38f; q.rad = 1e36f; break;
+        }
+    };
+    if (kind == 10) { for (int i = 4; i < n; i++) v[i].rad = -v[i].rad; return; }
+    if (kind == 11) { for (int i = 4; i < n; i++) v[i].p.x = v[i].p.y = v[i].p.z = NAN; return; }
+    int j = 0;
+    for (int i = 20; i < n; i += 7, j++) one(v[i], kind == 12 ? j % 10 : kind, j);
+}
+
+bool same_sections(const State *A, const State *B)
+{
+    auto eq = [](const auto &a, const auto &b) { return a.size() == b.size() && !memcmp(a.data(), b.data(), a.size() * sizeof(a[0])); };
+    return eq(A->nodes, B->nodes) && eq(A->geo, B->geo) && eq(A->ids, B->ids) && eq(A->words, B->words) && eq(A->maxid, B->maxid);
+}
+
+int run_degenerate(int n, float half, int nrays)
+{
+    const std::vector<rt_sphere> base = scene(n, half);
+    State *fresh = create(base.data(), n, 1);
+    if (!fresh) return 1;
+    std::vector<float> rays, maxt;
+    for (int k = 0; k < nrays; k++) {
+        float d[3] = {(float)(2 * uni() - 1), (float)(2 * uni() - 1), (float)(2 * uni() - 1)};
+        const float l = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) + 1e-9f;
+        for (int a = 0; a < 3; a++) rays.push_back((float)((2 * uni() - 1) * half));
+        for (int a = 0; a < 3; a++) rays.push_back(d[a] / l);
+        maxt.push_back((float)(uni() * 2 * half));
+    }
+    int rc = 0;
+    for (int kind = 0; kind <= 12; kind++) {
+        std::vector<rt_sphere> v = base;
+        degenerate(v, kind);
+        State *built = create(v.data(), n, 1), *S = create(base.data(), n, 1);
+        if (!built || !S) return 1;
+        char msg[256] = "";
+        long long bad = check(built, msg, sizeof(msg));
+        long long wrong = walk_check(built, rays.data(), nullptr, nrays, nullptr, nullptr) +
+                          walk_check(built, rays.data(), maxt.data(), nrays, nullptr, nullptr);
+        refit(S, v.data());
+        bad += check(S, msg, sizeof(msg));
+        wrong += walk_check(S, rays.data(), nullptr, nrays, nullptr, nullptr) +
+                 walk_check(S, rays.data(), maxt.data(), nrays, nullptr, nullptr);
+        refit(S, base.data());
+        const bool back = same_sections(S, fresh);
+        printf("n %d degenerate kind %d: violations %lld %s walk mismatches %lld refit back %s\n", n, kind, bad, msg, wrong,
+               back ? "equal" : "DIFFERS");
+        if (bad || wrong || !back) rc = 1;
+        delete built;
+        delete S;
+    }
+    delete fresh;
+    return rc;
+}
 }  // namespace
 
 int main()
 {
     const int a = run(300, 5.f), b = run(3000, 30.f);
-    return a | b;
+    const int c = run_degenerate(300, 5.f, 2000), d = run_degenerate(3000, 30.f, 500);
+    return a | b | c | d;
 }
 #endif

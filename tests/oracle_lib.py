@@ -77,6 +77,7 @@ def lib():
         L.ors_render.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int, _u64p, C.c_int]
+        L.ors_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.ors_hypersphere.argtypes = [C.POINTER(Sphere), C.c_int, C.c_double]
         L.orq_scene_init.argtypes = [C.POINTER(QPrimitive), C.c_int]
         L.orq_render.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -155,6 +156,16 @@ def smallpt_render(spheres, n, cam, colors, seeds_arr, pixels, w, h, first_sampl
                      pixels.ctypes.data, w, h, row_begin, row_end, first_sample, nsamples, dl,
                      cnt, nthreads)
     return list(cnt)
+
+
+def smallpt_pack(colors, w, h):
+    """The reference's pixel pack (smallptCPU.cpp:120-122) of a w x h
+    accumulator (float32 [3 w h]): uint32 [w h]."""
+    colors = np.ascontiguousarray(colors, dtype=np.float32)
+    assert colors.size == 3 * w * h
+    pixels = np.zeros(w * h, np.uint32)
+    lib().ors_pack(colors.ctypes.data, pixels.ctypes.data, w, h)
+    return pixels
 
 
 def hypersphere(max_depth, cap):

@@ -1,7 +1,7 @@
 """Shared plumbing of the refit tests (tests/test_refit.py on the CPU,
 tests/test_gpu_scene_update.py on the GPU): the native check
 (tests/native/spt_refit_check.cpp, built here with one g++ call into a
-temporary directory), the eight scenes, the five edits and the ray families.
+temporary directory), the nine scenes, the five edits and the ray families.
 
 TEST INFRASTRUCTURE ONLY (imported like oracle_lib and scenes_layouts)."""
 import atexit
@@ -112,9 +112,10 @@ SCENES = {
     "cloud30000": lambda: sl.cloud(sl.N_LEAF12),
     "cloud43000": lambda: sl.cloud(sl.N_LEAF16),
     "cloud56000": lambda: sl.cloud(sl.N_NOWIDE),
+    "degenerate": sl.degenerate_base,       # the cloud the degenerate kinds of scenes_layouts.py edit
 }
 LEAF = {"n256": 8, "no_always": 8, "many_always": 8, "coincident": 8, "cloud3000": 8, "cloud30000": 12,
-        "cloud43000": 16, "cloud56000": 0}
+        "cloud43000": 16, "cloud56000": 0, "degenerate": 8}
 
 
 def raw_rows(S, n):

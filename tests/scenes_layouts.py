@@ -197,6 +197,98 @@ def coincident_camera(w, h):
     return camera((-0.5, 0.6, 5.8), (-0.6, 0.2, 0.0), w, h)
 
 
+# ---- degenerate sphere data: negative, zero and non-finite radii and centres
+# The reference uses a radius only as rad * rad (geomfunc.h:42): a sphere of
+# radius -2 is the sphere of radius 2, and a sphere with a non-finite radius
+# or centre is never hit.  Each kind edits radii and centres of the 300-sphere
+# small cloud; the ground and the lights (indices 0..3) stay as they are.
+DEGENERATE_N, DEGENERATE_SMALL_N = 300, 40
+DEGENERATE_IDX = np.arange(20, 300, 7)                                   # 40 indices
+DEGENERATE_SMALL_IDX = np.arange(5, 40, 3)                               # 12 indices
+DEGENERATE_KINDS = ("neg", "neg_all", "zero", "denorm", "rad_inf", "rad_ninf", "rad_nan", "c_nan", "c_inf",
+                    "c_huge", "tree_nan", "mixed")
+DEGENERATE_SMALL_KINDS = ("neg", "rad_inf", "c_nan")
+_MIXED = ("neg", "zero", "denorm", "rad_inf", "rad_ninf", "rad_nan", "c_nan", "c_inf", "c_huge")
+
+
+def degenerate_base_rows(n=DEGENERATE_N):
+    return cloud_rows(n, 7, _SMALL_HALF, _SMALL_EXP)
+
+
+def _degenerate_edit(rows, kind, idx):
+    """Edit `kind` on the spheres `idx` of rows, in place."""
+    j = np.arange(len(idx))
+    if kind == "neg":
+        rows[idx, 0] *= f32(-4.0)
+    elif kind == "zero":
+        rows[idx, 0] = 0.0
+    elif kind == "denorm":
+        rows[idx, 0] = f32(1e-40)
+    elif kind == "rad_inf":
+        rows[idx, 0] = np.inf
+    elif kind == "rad_ninf":
+        rows[idx, 0] = -np.inf
+    elif kind == "rad_nan":
+        rows[idx, 0] = np.nan
+    elif kind == "c_nan":
+        rows[idx, 1 + j % 3] = np.nan
+    elif kind == "c_inf":
+        rows[idx, 1 + j % 3] = np.where(j % 2 == 0, np.inf, -np.inf).astype(f32)
+    elif kind == "c_huge":
+        # centre 3.4e38 on one axis, sign alternating; every second one with a
+        # radius large enough that c + rad overflows (the others' boxes are finite)
+        rows[idx, 1 + j % 3] = np.where(j % 4 < 2, 3.4e38, -3.4e38).astype(f32)
+        rows[idx[1::2], 0] = f32(1e36)
+    else:
+        raise KeyError(kind)
+
+
+def degenerate_rows(kind, n=DEGENERATE_N):
+    rows = degenerate_base_rows(n)
+    idx = DEGENERATE_IDX if n == DEGENERATE_N else DEGENERATE_SMALL_IDX
+    if kind == "neg_all":
+        rows[4:, 0] = -rows[4:, 0]
+    elif kind == "tree_nan":
+        rows[4:, 1:4] = np.nan
+    elif kind == "mixed":
+        for k, name in enumerate(_MIXED):
+            _degenerate_edit(rows, name, idx[k::len(_MIXED)])
+    else:
+        _degenerate_edit(rows, kind, idx)
+    return rows
+
+
+def degenerate(kind):
+    """The 300-sphere small cloud (a hierarchy scene) with edit `kind`."""
+    return pack(degenerate_rows(kind))
+
+
+def degenerate_base():
+    return pack(degenerate_base_rows())
+
+
+def degenerate_small(kind):
+    """The same edits on 12 of the cloud's first 40 spheres: scanned in full."""
+    return pack(degenerate_rows(kind, DEGENERATE_SMALL_N))
+
+
+degenerate_camera = small_camera
+
+
+def nonfinite_colours():
+    """The 40-sphere cloud with the emitter (inf, 3e38, 20), every other
+    emitter off and a zero channel in every diffuse colour: inf x 0 puts NaNs
+    into the accumulators, 3e38 sums overflow to inf."""
+    rows = degenerate_base_rows(DEGENERATE_SMALL_N)
+    rows[1, 4:7] = [np.inf, 3e38, 20.0]
+    rows[2:4, 4:7] = 0.0
+    rows[2:4, 7:10] = 0.5
+    diff = np.flatnonzero(rows[:, 10] == DIFF)
+    diff = diff[diff != 1]
+    rows[diff, 7 + diff % 3] = 0.0
+    return pack(rows)
+
+
 EDGE_SCENES = {
     "no_always": (lambda: no_always(), no_always_camera),
     "many_always": (lambda: many_always()[0], many_always_camera),

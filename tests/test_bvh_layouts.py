@@ -92,6 +92,34 @@ def test_edge_scenes_are_what_they_claim(chk):
     assert c["leaf_max"] == 8 and c["wdepth"] >= 2, c
 
 
+@pytest.mark.parametrize("kind", sl.DEGENERATE_KINDS)
+def test_degenerate_scenes_get_a_leaf8_hierarchy(chk, kind):
+    """Negative, zero and non-finite radii and centres do not change the class
+    the tests built on these scenes assume: an 8-wide tree with leaves of 8.
+    The partition goes by |rad| against 64 x the median |rad| (NaNs apart):
+    the first 16 spheres above it in index order are always spheres, so with
+    40 infinite radii most of them land inside the tree."""
+    S, n = sl.degenerate(kind)
+    assert n == sl.DEGENERATE_N >= 256
+    c = choice(chk, S, n)
+    assert c["leaf_max"] == 8 and c["wdepth"] >= 2 and c["wnodes"] >= 2 and c["lds"] <= WIDE_LDS_MAX, c
+    r = np.abs(sl.degenerate_rows(kind)[:, 0])
+    with np.errstate(invalid="ignore"):
+        big = int((r > np.float32(64) * np.sort(r[~np.isnan(r)])[(~np.isnan(r)).sum() // 2]).sum())
+    assert c["nalways"] == min(big, 16) >= 1, (c, big)
+    if kind in ("rad_inf", "rad_ninf"):
+        assert big == 41 and c["nalways"] == 16
+    if kind == "neg_all":
+        base = choice(chk, *sl.degenerate_base())
+        assert {k: c[k] for k in ("wnodes", "wdepth", "nalways", "lds")} == {k: base[k] for k in ("wnodes", "wdepth", "nalways", "lds")}
+
+
+def test_small_degenerate_scenes_are_scanned_in_full():
+    for kind in sl.DEGENERATE_SMALL_KINDS:
+        assert sl.degenerate_small(kind)[1] == sl.DEGENERATE_SMALL_N < 256
+    assert sl.nonfinite_colours()[1] < 256
+
+
 def _rays(rng, rows, origin, nr, spread):
     """Origins around sphere centres and at the camera, random directions,
     some with an exactly zero component (the walk's 1e-30 clamp)."""

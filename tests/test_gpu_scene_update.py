@@ -123,7 +123,9 @@ def _differs(a, b):
 @pytest.mark.parametrize("name", list(rc.SCENES))
 def test_device_refit_equals_host_arithmetic(rt, world, monkeypatch, name):
     """Edits 1..5 in turn on one prepared scene: after each update the five
-    sections the device holds are the host refit's, byte for byte."""
+    sections the device holds are the host refit's, byte for byte.  On the
+    degenerate kinds' base cloud, three more steps per kind: to the kind, back,
+    and the base again against the builders' bytes."""
     _clean(monkeypatch)
     S, n, rows = world[0](name)
     host = rc.Host(S, n)
@@ -147,6 +149,28 @@ def test_device_refit_equals_host_arithmetic(rt, world, monkeypatch, name):
             ui = sc.update_info()
             assert ui["updates"] == k and ui["refits"] == k and ui["reallocations"] == 0, ui
             assert ui["metadata_bytes"] == host.meta_bytes, (ui, host.meta_bytes)
+        if name == "degenerate":
+            # Negative, zero and non-finite radii and centres (scenes_layouts.degenerate): base to each
+            # kind, that kind back to base, and base again -- which must be the builders' bytes.
+            updates = len(rc.EDITS)
+            builders = rc.Host(S, n)
+            fresh = {k: v.copy() for k, v in builders.sections().items()}
+            builders.close()
+            for kind in sl.DEGENERATE_KINDS:
+                for step, arr in ((kind, sl.degenerate(kind)[0]), ("back from " + kind, S), ("base again", S)):
+                    sc.update(arr)
+                    updates += 1
+                    got, want = sc.hierarchy(), host.refit(arr).sections()
+                    if step == "base again":
+                        want = fresh
+                    for sec in rc.SECTIONS:
+                        a, b = got[sec].view(np.uint32), want[sec].view(np.uint32)
+                        assert a.shape == b.shape
+                        assert (a == b).all(), "%s, %s: %d words differ, first at %s" % (
+                            step, sec, (a != b).sum(), np.argwhere(a != b)[0])
+                    assert host.check() == (0, ""), step
+            ui = sc.update_info()
+            assert ui["updates"] == updates and ui["refits"] == updates and ui["reallocations"] == 0, ui
         assert sc.info()["leaf_max"] == info["leaf_max"] and sc.info()["family"] == info["family"]
     finally:
         sc.close()
