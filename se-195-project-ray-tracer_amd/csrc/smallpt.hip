@@ -327,6 +327,29 @@ __device__ __forceinline__ bool shadow_bf(const G &geo, const ray3 &rs, float ma
     return occ;
 }
 
+// shadow_bf for a flush pass: the lane mask of the rays that reached the
+// light (have && !occluded).  The two ballots are of compares, so the mask
+// stays in scalar registers; ballot(have && !occ) of the merged flags went
+// through a VGPR and back.
+template <class G>
+__device__ __forceinline__ unsigned long long shadow_bf_unocc(const G &geo, const ray3 &rs, float maxt, bool have)
+{
+    uint32_t near = acc::KEY_NONE;
+    const bool bad = for_spheres_bf(geo, rs, [&](int, int, float t1, float t2) { acc::any_accept(near, t1, t2); }, [](int) {});
+    const unsigned long long hm = __builtin_amdgcn_ballot_w64(have);
+    // (the limit key behind an opaque copy: folded into the compare, its
+    // select becomes an AND of two compares, which is no compare to a ballot)
+    uint32_t lim = acc::limit_key(maxt);
+    asm volatile("" : "+v"(lim));
+    unsigned long long un = hm & ~__builtin_amdgcn_ballot_w64(near < lim);
+    if (wave_any(have && bad)) {
+        float ts = maxt;
+        int first = -1;
+        un = hm & __builtin_amdgcn_ballot_w64(query<false>(geo, rs, ts, first) < 0);
+    }
+    return un;
+}
+
 // ---------------------------------------------------------------------------
 // The sphere hierarchy's device code for large scenes -- BvhView, the binary
 // walk, the 8-wide walk in LDS and its cooperative form -- stands here, inside
@@ -348,7 +371,10 @@ enum { PB_ITER, PB_SHADOW, PB_NEAREST, PB_DIFF, PB_SPEC, PB_REFR, PB_LIGHT, PB_B
        // flush passes by what started them (the first that holds, in this order):
        // the threshold, a DIFF hit with no free slot, a sample ending behind a
        // parked one, an emitter term behind an unresolved entry, the drain
-       PB_FL_THRESH, PB_FL_SLOT, PB_FL_ENDS, PB_FL_EMIT, PB_FL_DRAIN, PB_N };
+       PB_FL_THRESH, PB_FL_SLOT, PB_FL_ENDS, PB_FL_EMIT, PB_FL_DRAIN,
+       // the owners' step of a flush pass: entries resolved / passes with one,
+       // lanes and passes that fold a parked sample, lanes that resolve one entry / two
+       PB_OW_ROUND, PB_OW_FOLD, PB_OW_ONE, PB_OW_TWO, PB_N };
 __device__ unsigned long long g_spt_prof[2 * PB_N];
 #define SPT_PROF(b)                                                                        \
     do {                                                                                   \
@@ -942,36 +968,50 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                             if (lane == 0 && b == why) prof_w[b]++;
                         }
                     })
-                    const bool occ = shadow_bf(geo, rs, maxt, have);
-                    const unsigned long long unocc = __builtin_amdgcn_ballot_w64(have && !occ);
-                    // owners, oldest entry first (:154-161, then :229-230).  (The
-                    // fold stands inside the loop: hoisted behind it, to run once a
-                    // pass, it cost 13 more scalar spills and 2.3 % of the frame;
-                    // tried again with the lane's address held: 14 more, 2.9 %.)
-                    while (npend > 0) {
-                        const int rel = sptpolicy::sq_rel(pidx & 255, q_head);
-                        if (rel >= m) break;
-                        const bool lit = (unocc >> rel) & 1ull;
-                        if (npark > 0) {
-                            float *p = park_ptr();
-                            if (lit) {
-                                p[64 * SLOT_RAD] = p[64 * SLOT_RAD] + pc0.x;
-                                p[64 * (SLOT_RAD + 1)] = p[64 * (SLOT_RAD + 1)] + pc0.y;
-                                p[64 * (SLOT_RAD + 2)] = p[64 * (SLOT_RAD + 2)] + pc0.z;
+                    const unsigned long long unocc = shadow_bf_unocc(geo, rs, maxt, have);
+                    // owners (:154-161, then :229-230): a lane's popped entries, at most
+                    // two, resolved in straight-line code, oldest first -- parked terms
+                    // onto the parked rad (one load and one store of SLOT_RAD), the
+                    // fold at most once, the other terms onto rad, then the shift.
+                    // (The per-entry loop this replaces ran 2.0 rounds a pass, each with
+                    // its own exec-mask bookkeeping, and folded in 1.6 of them.)
+                    const sptpolicy::SqOwners ow = sptpolicy::sq_owners(pidx, npend, q_head, m, unocc);
+                    if (ow.r0) {
+                        SPT_PROF(PB_OW_ROUND);
+                        SPT_PROF_ONLY(if (ow.r1) prof_l[PB_OW_ROUND]++;)
+                        SPT_PROF_ONLY(if (ow.r1) SPT_PROF(PB_OW_TWO); else SPT_PROF(PB_OW_ONE);)
+                        const int nres = sptpolicy::sq_owners_resolved(ow);
+                        const int nparked = sptpolicy::sq_owners_parked(nres, npark);
+                        float *p = park_ptr();
+                        v3 pc1 = pc0;           // the second term: resolved now, or the oldest from here on
+                        if (npend == 2) pc1 = mk(p[64 * SLOT_PEND], p[64 * (SLOT_PEND + 1)], p[64 * (SLOT_PEND + 2)]);
+                        if (nparked > 0) {
+                            v3 pr = mk(p[64 * SLOT_RAD], p[64 * (SLOT_RAD + 1)], p[64 * (SLOT_RAD + 2)]);
+                            const bool add0 = ow.lit0, add1 = nparked == 2 && ow.lit1;
+                            if (add0) pr = vadd(pr, pc0);
+                            if (add1) pr = vadd(pr, pc1);
+                            if (add0 || add1) {
+                                p[64 * SLOT_RAD] = pr.x;
+                                p[64 * (SLOT_RAD + 1)] = pr.y;
+                                p[64 * (SLOT_RAD + 2)] = pr.z;
                             }
-                            npark--;
-                            if (npark == 0)
-                                fold(mk(p[64 * SLOT_RAD], p[64 * (SLOT_RAD + 1)], p[64 * (SLOT_RAD + 2)]),
-                                     first_sample + k - 1);
-                        } else if (lit) {
+                            if (nparked == npark) {
+                                SPT_PROF(PB_OW_FOLD);
+                                // (an opaque copy: the compiler otherwise hoists the fold's
+                                // int-to-float and rcp_nr in front of the flush loop, into
+                                // every iteration -- seven VALU operations and two registers)
+                                int prev = first_sample + k - 1;
+                                asm volatile("" : "+v"(prev));
+                                fold(pr, prev);
+                            }
+                        } else if (ow.lit0) {
                             rad = vadd(rad, pc0);
                         }
-                        npend--;
-                        pidx >>= 8;
-                        if (npend > 0) {
-                            const float *p = park_ptr();
-                            pc0 = mk(p[64 * SLOT_PEND], p[64 * (SLOT_PEND + 1)], p[64 * (SLOT_PEND + 2)]);
-                        }
+                        if (ow.lit1 && nparked < 2) rad = vadd(rad, pc1);
+                        npark -= nparked;
+                        npend -= nres;
+                        pidx = sptpolicy::sq_owners_shift(pidx, nres);
+                        pc0 = pc1;
                     }
                     q_head = __builtin_amdgcn_readfirstlane(sptpolicy::sq_wrap(q_head + m));
                     q_count = __builtin_amdgcn_readfirstlane(q_count - m);
@@ -1074,7 +1114,7 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                         specular = false;
                         thr = vmul(thr, mk(oc.x, oc.y, oc.z));
                         lsum = mk(0.f, 0.f, 0.f);
-                        li = 0;
+                        if constexpr (!DUAL) li = 0;            // (DUAL: the only light, no index)
                         lights = true;
                     } else if (refl == SPEC) {
                         SPT_PROF(PB_SPEC);
@@ -1089,7 +1129,10 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                         a_R = true;                             // ray, hit, nl, dp, inv_sign, id -> pass A
                     }
                     depth++;
-                    done = done || (!lights && !a_R && depth > 6);   // :184 at the next bounce
+                    // :184 at the next bounce.  (A REFR lane's test follows its pass A
+                    // below; DUAL: taken here -- done is false on that side, pass A does
+                    // not read it, and the merge behind pass A cost five VALU operations.)
+                    done = done || (!lights && (DUAL || !a_R) && depth > 6);
                 }
             }
 
@@ -1100,7 +1143,8 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
             // drawn second-first, as the g++-built oracle does (:138); the
             // Russian-roulette draw of REFR is taken before its Fresnel terms
             // (no other draw of the lane lies between).
-            bool a_L = lights && li < S.nlights;
+            // (DUAL: one light, so every lane at a DIFF hit samples it.)
+            bool a_L = DUAL ? lights : lights && li < S.nlights;
             bool lights_done = lights && !a_L;
             const bool was_R = a_R;
             // One pass for every lane that needs A, then further light-only
@@ -1115,7 +1159,8 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                     // discarded by the selects below; li is clamped into the
                     // light list) -- a conditional load left five zeroing
                     // moves and a branch in every pass.
-                    const int lj = li < S.nlights ? li : 0;
+                    // (DUAL: the only light's record, at its fixed address.)
+                    const int lj = DUAL ? 0 : (li < S.nlights ? li : 0);
                     const float4 lg = S.lrec[3 * lj];           // centre
                     const float4 lc = S.lrec[3 * lj + 1];       // colour.xyz, rad
                     // REFR terms (:281-296), rebuilt here from the few values
@@ -1151,7 +1196,10 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                     const v3 vv = (!with_r || a_L) ? vl : vr;
                     const float dd = vdot(vv, vv);
                     float len, ilen;                            // sqrtf(dd), 1.f / len
-                    if (!wave_any(!sqrt_nr_ok(dd))) {
+                    // (DUAL: the short forms fall through; the other kernels' layout is
+                    // left as it was -- the hint costs them four to six scalar instructions)
+                    const bool in_range = !wave_any(!sqrt_nr_ok(dd));
+                    if (DUAL ? __builtin_expect(in_range, 1) : in_range) {
                         len = sqrt_nr(dd);
                         ilen = rcp_nr(len);
                     } else {
@@ -1194,16 +1242,18 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                             rg[6 * SQ_RING + pos] = len - EPS;
                             const float4 le = S.lrec[2];
                             const v3 c = vmul(thr, vsmul(quo, mk(le.x, le.y, le.z)));   // 0 + e * s, then thr * Ld
-                            if (npend == 0) {
-                                pc0 = c;
-                                pidx = pos;
-                            } else {
-                                float *p = park_ptr();
-                                p[64 * SLOT_PEND] = c.x;
-                                p[64 * (SLOT_PEND + 1)] = c.y;
-                                p[64 * (SLOT_PEND + 2)] = c.z;
-                                pidx |= pos << 8;
-                            }
+                            // (Selects and an unconditional store, not two branch
+                            // sides: the sides met in seven register copies on every
+                            // push.  A lane with nothing pending writes the second
+                            // entry's slot too; nothing reads it before the next push
+                            // with one entry pending rewrites it.)
+                            const bool first_term = npend == 0;
+                            float *p = park_ptr();
+                            p[64 * SLOT_PEND] = c.x;
+                            p[64 * (SLOT_PEND + 1)] = c.y;
+                            p[64 * (SLOT_PEND + 2)] = c.z;
+                            pc0 = mk(first_term ? c.x : pc0.x, first_term ? c.y : pc0.y, first_term ? c.z : pc0.z);
+                            pidx = first_term ? pos : (pidx | pos << 8);
                             npend++;
                             pushed = true;
                             a_L = false;
@@ -1219,6 +1269,9 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
                             shadow = true;
                             a_L = false;
                             if (DUAL) lights_done = true;       // the only light
+                        } else if constexpr (DUAL) {
+                            a_L = false;
+                            lights_done = true;                 // the only light
                         } else {
                             li++;
                             a_L = li < S.nlights;
@@ -1254,15 +1307,20 @@ render_kernel(const rt_sphere *__restrict__ spheres, int nspheres, rt_camera cam
             // li = 1 = nlights); the scalar test keeps the light-only loop --
             // and the copies of the loop-carried state the compiler puts at
             // its header, 12 VALU ops per iteration -- out of such scenes.
-            if (S.nlights > 1) {
-                while (wave_any(a_L)) {
-                    if (a_L) pass_a(false);
+            // A DUAL kernel runs only such scenes and has no such loop.
+            if constexpr (!DUAL) {
+                if (S.nlights > 1) {
+                    while (wave_any(a_L)) {
+                        if (a_L) pass_a(false);
+                    }
                 }
             }
             if constexpr (DQ)      // this iteration's pushes (one pass A: every lane is back here)
                 q_count = __builtin_amdgcn_readfirstlane(
                     q_count + __builtin_popcountll(__builtin_amdgcn_ballot_w64(pushed)));
-            if (was_R) done = depth > 6;
+            if constexpr (!DUAL) {
+                if (was_R) done = depth > 6;
+            }
             if (lights_done) {                                 // :229-230, then the bounce
                 // (DUAL: Ld is 0 + e * s once the pending shadow ray is
                 // resolved, or 0 -- and rad + thr * 0 == rad -- if none.)

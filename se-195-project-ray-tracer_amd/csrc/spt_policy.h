@@ -78,6 +78,28 @@ SPT_HD constexpr int sq_push_pos(int head, int count, int rank) { return sq_wrap
 // an entry's distance from the head: it is among the m popped ones iff < m
 SPT_HD constexpr int sq_rel(int pos, int head) { return pos - head < 0 ? pos - head + SQ_RING : pos - head; }
 
+// The owners' step of a flush pass.  A lane holds up to two entries, oldest
+// first, at the ring positions in pidx's bytes 0 and 1 (npend of them), of
+// which the oldest npark belong to its parked sample.  The pass pops the m
+// entries from head; unocc has the bit of every popped entry whose ray
+// reached the light.  FIFO: the second entry resolves only if the first does
+// (tests/native/owners_step_check.cpp: against the per-entry loop).
+struct SqOwners {
+    bool r0, r1;        // the oldest / the second entry is among the popped ones
+    bool lit0, lit1;    //   ... and its ray reached the light
+};
+SPT_HD constexpr SqOwners sq_owners(int pidx, int npend, int head, int m, unsigned long long unocc)
+{
+    const int rel0 = sq_rel(pidx & 255, head), rel1 = sq_rel((pidx >> 8) & 255, head);
+    const bool r0 = npend > 0 && rel0 < m, r1 = r0 && npend > 1 && rel1 < m;
+    return SqOwners{r0, r1, r0 && ((unocc >> (rel0 & 63)) & 1ull) != 0, r1 && ((unocc >> (rel1 & 63)) & 1ull) != 0};
+}
+// the entries the lane drops from its list, how many of n dropped ones belong
+// to the parked sample, and the list's positions after n are dropped
+SPT_HD constexpr int sq_owners_resolved(const SqOwners &o) { return o.r1 ? 2 : (o.r0 ? 1 : 0); }
+SPT_HD constexpr int sq_owners_parked(int n, int npark) { return n < npark ? n : npark; }
+SPT_HD constexpr int sq_owners_shift(int pidx, int n) { return pidx >> (8 * n); }
+
 // prio_sched: the three priority-level boundaries, 8 bits each, in 1/256 of
 // the samples.
 inline int pack_prio(int a, int b, int c) { return (a & 255) | ((b & 255) << 8) | ((c & 255) << 16); }

@@ -55,7 +55,10 @@ def child():
                  "wcall", "wstep", "wleaf", "wshade", "flush",   # flush: ring entries popped / passes
                  # ... and the same by what started the pass: threshold, no free slot,
                  # previous sample unfolded, emitter term, drain
-                 "fl_thr", "fl_slot", "fl_ends", "fl_emit", "fl_drain"]
+                 "fl_thr", "fl_slot", "fl_ends", "fl_emit", "fl_drain",
+                 # the owners' step of a flush pass: entries resolved (waves: passes that resolve one),
+                 # folds of a parked sample, and per pass the lanes that resolve one entry / two
+                 "ow_round", "ow_fold", "ow_one", "ow_two"]
         buf = (C.c_ulonglong * (2 * max(len(names), 64)))()   # (room for a build with more counters than names)
         L.spt_prof_read(buf)
         for b, nm in enumerate(names):
