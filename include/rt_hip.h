@@ -493,6 +493,73 @@ int spt_scene_render_pixels_async(const spt_scene *scene, const rt_camera *camer
                                   const int32_t *d_list, const int32_t *d_take, size_t nlist, int nsamples,
                                   int32_t *d_done, int first_sample, int mode, void *stream);
 
+/* The same call, keeping a second-moment plane beside the colour: what an
+ * adaptive sampler needs to decide where the next samples go.
+ *
+ * d_m2: required, device memory, w*h floats at the colour slot (h-y-1)*w+x;
+ * it must not alias the other buffers.  Everything
+ * spt_scene_render_pixels_async specifies holds unchanged: colours, seeds,
+ * d_pixels and d_done come out bit for bit as from that call with the same
+ * arguments.  In addition, for a listed pixel with take t > 0 whose first
+ * sample has number `base`, each sample j with radiance R (the value folded
+ * into the colour) folds
+ *     q  = (R.x*R.x + R.y*R.y) + R.z*R.z            (float, unfused)
+ *     m2 = (base + j == 0) ? q : (m2*k1 + q)*k2     (the colour fold's k1, k2)
+ * so d_m2[slot] is the running mean of |R|^2 as d_colors is the running mean
+ * of R: read when base > 0, written together with the colour.  With the
+ * stored colour c, m2 - |c|^2 is the summed per-channel variance of the
+ * pixel's samples.  A sample whose camera ray is non-finite folds q = 0; a
+ * take of 0, an entry outside the frame and an unlisted pixel leave
+ * d_m2[slot] untouched; a non-finite R gives whatever the expressions give.
+ *
+ * Asynchronous, capturable and validated as spt_scene_render_pixels_async;
+ * RT_ERR_INVALID also for a null d_m2.  RT_SPT_QUERY_BLOCKS applies. */
+int spt_scene_render_pixels_stats_async(const spt_scene *scene, const rt_camera *camera,
+                                        float *d_colors, const uint32_t *d_seeds_in, uint32_t *d_seeds_out,
+                                        uint32_t *d_pixels, float *d_m2, int w, int h,
+                                        const int32_t *d_list, const int32_t *d_take, size_t nlist, int nsamples,
+                                        int32_t *d_done, int first_sample, int mode, void *stream);
+
+/* ------------------------------------------------------------ smallpt, the sample plan */
+/* The next pixel list of a frame, built on the device from its colours,
+ * second moments and sample counts: "render until every pixel's relative
+ * standard error is below tol, at most max_samples samples" is K x (plan,
+ * render) enqueued back to back, or one graph.  No scene is involved.
+ *
+ * Per slot i, with n = d_done[i] and c its colour, in float, unfused:
+ *   n < min_samples:  take = min_samples - n, e = +inf
+ *   otherwise:        mean2 = (c.x*c.x + c.y*c.y) + c.z*c.z
+ *                     var   = d_m2[i] - mean2;  var = var > 0 ? var : 0   (NaN -> 0)
+ *                     e     = sqrtf(var / ((float)n * (mean2 + floor)))
+ *                     take  = (e > tol && n < max_samples) ? min(step, max_samples - n) : 0
+ * (a NaN e is not listed; the n/(n-1) factor is left out: min_samples guards
+ * small n).  The pixels with take > 0 go to d_list[j] = y*w+x, d_take[j], in
+ * 8 x 8 tile order -- ascending ((y>>3)*tiles_x + (x>>3))*64 + (y&7)*8 + (x&7),
+ * tiles_x = (w+7)/8 -- entries of rank >= cap are dropped, and every position
+ * from the number written up to cap gets d_list = -1, d_take = 0: the caller
+ * passes nlist = cap to spt_scene_render_pixels*_async whatever was listed.
+ * d_error: nullable, w*h floats at the slot: e.  d_totals: nullable, 2 words:
+ * the pixels listed (before truncation) and the sum of their takes.
+ * d_scratch: device memory of spt_frame_plan_scratch_bytes(w, h) bytes (0 for
+ * a frame size that is not valid), 16-byte aligned, the call's alone until it
+ * has run; its contents mean nothing to the caller.
+ *
+ * Three stream-ordered launches; asynchronous, allocates nothing, never
+ * synchronises, keeps no state: any number of calls may be captured.
+ * cap == 0 writes only d_error / d_totals.  RT_ERR_INVALID: a null d_colors,
+ * d_m2, d_done, params or d_scratch, a null d_list or d_take unless cap == 0;
+ * w or h < 1, or w*h above INT32_MAX; min_samples < 1, max_samples <
+ * min_samples or step < 1; a NaN or negative tol or floor; cap above
+ * INT32_MAX. */
+typedef struct {
+    int32_t min_samples, max_samples, step;
+    float tol, floor;
+} spt_plan_params;
+size_t spt_frame_plan_scratch_bytes(int w, int h);
+int spt_frame_plan_async(const float *d_colors, const float *d_m2, const int32_t *d_done, int w, int h,
+                         const spt_plan_params *params, int32_t *d_list, int32_t *d_take, size_t cap,
+                         float *d_error, uint64_t *d_totals, void *d_scratch, void *stream);
+
 /* ------------------------------------------------------------ smallpt, several GPUs */
 /* One frame tiled over the GPUs of a node in row bands:
  * band k owns the k-th contiguous chunk of the flipped colour / seed slots,

@@ -1577,6 +1577,10 @@ __global__ void __launch_bounds__(256) list_dedup_kernel(const int *__restrict__
 // same estimator for the pixels the caller lists, a sample count per entry.
 #include "spt_pixels.h"
 
+// The sample plan (spt_frame_plan_async): colours, second moments and sample
+// counts into the next pixel list, in three stream-ordered launches.
+#include "spt_plan.h"
+
 }  // namespace smallpt
 }  // namespace rt
 
@@ -2283,36 +2287,43 @@ extern "C" int spt_scene_radiance_async(const spt_scene *sc, const float *d_rays
 
 // ---- pixel lists (spt_pixels.h)
 namespace {
-using PixelsKernel = decltype(&rt::smallpt::pixels_kernel<0, false>);
+template <bool STATS>
+using PixelsKernel = decltype(&rt::smallpt::pixels_kernel<0, false, STATS>);
 
-template <int GEO>
-PixelsKernel pick_pixels(bool dl)
+template <int GEO, bool STATS>
+PixelsKernel<STATS> pick_pixels(bool dl)
 {
-    return dl ? rt::smallpt::pixels_kernel<GEO, true> : rt::smallpt::pixels_kernel<GEO, false>;
+    return dl ? rt::smallpt::pixels_kernel<GEO, true, STATS> : rt::smallpt::pixels_kernel<GEO, false, STATS>;
 }
-}  // namespace
 
-extern "C" int spt_scene_render_pixels_async(const spt_scene *sc, const rt_camera *camera, float *d_colors,
-                                             const uint32_t *d_seeds_in, uint32_t *d_seeds_out, uint32_t *d_pixels,
-                                             int w, int h, const int32_t *d_list, const int32_t *d_take, size_t nlist,
-                                             int nsamples, int32_t *d_done, int first_sample, int mode, void *stream)
+template <bool STATS>
+PixelsKernel<STATS> pick_pixels(int geo, bool dl)
 {
+    return geo == GEO_WIDE  ? pick_pixels<GEO_WIDE, STATS>(dl)
+           : geo == GEO_BVH ? pick_pixels<GEO_BVH, STATS>(dl)
+           : geo == GEO_LDS ? pick_pixels<GEO_LDS, STATS>(dl)
+                            : pick_pixels<GEO_GLOBAL, STATS>(dl);
+}
+
+// Both pixel-list entry points: `who` names the caller in the messages;
+// stats: the second-moment plane d_m2 is kept (the STATS kernels).
+int render_pixels(const char *who, const spt_scene *sc, const rt_camera *camera, float *d_colors,
+                  const uint32_t *d_seeds_in, uint32_t *d_seeds_out, uint32_t *d_pixels, int w, int h,
+                  const int32_t *d_list, const int32_t *d_take, size_t nlist, int nsamples, int32_t *d_done,
+                  int first_sample, int mode, bool stats, float *d_m2, void *stream)
+{
+    const auto bad = [who](const char *what) { return rtrt::fail(RT_ERR_INVALID, (std::string(who) + ": " + what).c_str()); };
     if (!sc || !camera || !d_colors || !d_seeds_in || !d_seeds_out || !d_pixels || !d_list)
-        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: null scene, camera, colours, seeds, pixels or list");
-    if (w < 1 || h < 1 || (long long)w * h > (long long)INT32_MAX)
-        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: bad frame size");
-    if (nsamples < 0 || first_sample < 0)
-        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: negative nsamples or first_sample");
-    if (d_take && nsamples > 0)
-        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: nsamples must be 0 beside d_take");
-    if (d_done && first_sample > 0)
-        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: first_sample must be 0 beside d_done");
-    if (mode != SPT_PATH_TRACING && mode != SPT_DIRECT_LIGHTING)
-        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: unknown mode (no flags are taken)");
-    if (nlist > (size_t)INT32_MAX) return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: list too long");
+        return bad("null scene, camera, colours, seeds, pixels or list");
+    if (stats && !d_m2) return bad("null d_m2");
+    if (w < 1 || h < 1 || (long long)w * h > (long long)INT32_MAX) return bad("bad frame size");
+    if (nsamples < 0 || first_sample < 0) return bad("negative nsamples or first_sample");
+    if (d_take && nsamples > 0) return bad("nsamples must be 0 beside d_take");
+    if (d_done && first_sample > 0) return bad("first_sample must be 0 beside d_done");
+    if (mode != SPT_PATH_TRACING && mode != SPT_DIRECT_LIGHTING) return bad("unknown mode (no flags are taken)");
+    if (nlist > (size_t)INT32_MAX) return bad("list too long");
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != sc->device)
-        return rtrt::fail(RT_ERR_INVALID, "spt_scene_render_pixels_async: the scene's device is not the current one");
+    if (hipGetDevice(&dev) != hipSuccess || dev != sc->device) return bad("the scene's device is not the current one");
     if (nlist == 0) return RT_OK;
     // spt_scene_radiance_async's family, LDS bytes and grid: persistent
     // blocks over the list's chunks; RT_SPT_QUERY_BLOCKS caps the grid.
@@ -2335,12 +2346,70 @@ extern "C" int spt_scene_render_pixels_async(const spt_scene *sc, const rt_camer
                                     (int)nlist, nsamples, d_done, first_sample, sc->n, sc->nlights, sc->d_soa, opts,
                                     refill};
     const bool dl = mode == SPT_DIRECT_LIGHTING;
-    const PixelsKernel kern = geo == GEO_WIDE  ? pick_pixels<GEO_WIDE>(dl)
-                              : geo == GEO_BVH ? pick_pixels<GEO_BVH>(dl)
-                              : geo == GEO_LDS ? pick_pixels<GEO_LDS>(dl)
-                                               : pick_pixels<GEO_GLOBAL>(dl);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * wpb), lds, (hipStream_t)stream, a, sc->bvh);
-    return rtrt::check_launch("spt pixels_kernel");
+    if (stats) {
+        const rt::smallpt::PixelsStatsArgs as{a, d_m2};
+        hipLaunchKernelGGL(pick_pixels<true>(geo, dl), dim3((unsigned)nblocks), dim3(64 * wpb), lds, (hipStream_t)stream,
+                           as, sc->bvh);
+    } else {
+        hipLaunchKernelGGL(pick_pixels<false>(geo, dl), dim3((unsigned)nblocks), dim3(64 * wpb), lds, (hipStream_t)stream,
+                           a, sc->bvh);
+    }
+    return rtrt::check_launch(stats ? "spt pixels_kernel (stats)" : "spt pixels_kernel");
+}
+}  // namespace
+
+extern "C" int spt_scene_render_pixels_async(const spt_scene *sc, const rt_camera *camera, float *d_colors,
+                                             const uint32_t *d_seeds_in, uint32_t *d_seeds_out, uint32_t *d_pixels,
+                                             int w, int h, const int32_t *d_list, const int32_t *d_take, size_t nlist,
+                                             int nsamples, int32_t *d_done, int first_sample, int mode, void *stream)
+{
+    return render_pixels("spt_scene_render_pixels_async", sc, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h,
+                         d_list, d_take, nlist, nsamples, d_done, first_sample, mode, false, nullptr, stream);
+}
+
+extern "C" int spt_scene_render_pixels_stats_async(const spt_scene *sc, const rt_camera *camera, float *d_colors,
+                                                   const uint32_t *d_seeds_in, uint32_t *d_seeds_out,
+                                                   uint32_t *d_pixels, float *d_m2, int w, int h,
+                                                   const int32_t *d_list, const int32_t *d_take, size_t nlist,
+                                                   int nsamples, int32_t *d_done, int first_sample, int mode,
+                                                   void *stream)
+{
+    return render_pixels("spt_scene_render_pixels_stats_async", sc, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels,
+                         w, h, d_list, d_take, nlist, nsamples, d_done, first_sample, mode, true, d_m2, stream);
+}
+
+// ---- the sample plan (spt_plan.h)
+extern "C" size_t spt_frame_plan_scratch_bytes(int w, int h)
+{
+    if (w < 1 || h < 1 || (long long)w * h > (long long)INT32_MAX) return 0;
+    return rt::smallpt::plan_scratch_bytes(rt::smallpt::plan_tiles(w, h));
+}
+
+extern "C" int spt_frame_plan_async(const float *d_colors, const float *d_m2, const int32_t *d_done, int w, int h,
+                                    const spt_plan_params *params, int32_t *d_list, int32_t *d_take, size_t cap,
+                                    float *d_error, uint64_t *d_totals, void *d_scratch, void *stream)
+{
+    const auto bad = [](const char *what) { return rtrt::fail(RT_ERR_INVALID, what); };
+    if (!d_colors || !d_m2 || !d_done || !params || !d_scratch)
+        return bad("spt_frame_plan_async: null colours, second moments, counts, params or scratch");
+    if (cap > 0 && (!d_list || !d_take)) return bad("spt_frame_plan_async: null d_list or d_take");
+    if (w < 1 || h < 1 || (long long)w * h > (long long)INT32_MAX) return bad("spt_frame_plan_async: bad frame size");
+    if (params->min_samples < 1 || params->max_samples < params->min_samples || params->step < 1)
+        return bad("spt_frame_plan_async: min_samples < 1, max_samples < min_samples or step < 1");
+    if (!(params->tol >= 0.f) || !(params->floor >= 0.f))
+        return bad("spt_frame_plan_async: tol or floor negative or not a number");
+    if (cap > (size_t)INT32_MAX) return bad("spt_frame_plan_async: cap too large");
+    namespace sp = rt::smallpt;
+    const int ntiles = sp::plan_tiles(w, h);
+    const sp::PlanArgs a{d_colors, d_m2, d_done, w, h, ntiles, *params, d_list, d_take, (int)cap, d_error, d_totals,
+                         sp::plan_scratch_head(d_scratch), sp::plan_scratch_sums(d_scratch),
+                         sp::plan_scratch_counts(d_scratch, ntiles)};
+    const hipStream_t s = (hipStream_t)stream;
+    const dim3 tiles((unsigned)((ntiles + sp::PLAN_WPB - 1) / sp::PLAN_WPB)), waves(64 * sp::PLAN_WPB);
+    hipLaunchKernelGGL(sp::plan_count_kernel<sp::PLAN_WPB>, tiles, waves, 0, s, a);
+    hipLaunchKernelGGL(sp::plan_scan_kernel<sp::PLAN_SCAN_ITEMS>, dim3(1), dim3(sp::PLAN_SCAN_THREADS), 0, s, a);
+    if (cap > 0) hipLaunchKernelGGL(sp::plan_scatter_kernel<sp::PLAN_WPB>, tiles, waves, 0, s, a);
+    return rtrt::check_launch("spt plan kernels");
 }
 
 namespace {

@@ -114,8 +114,23 @@ struct PixelsArgs {
     int refill;                   // 0: the chunk-synchronous form
 };
 
-template <int GEO, bool DL>
-__global__ void __launch_bounds__(64 * query_wpb(GEO)) pixels_kernel(PixelsArgs a, BvhView bvh)
+// spt_scene_render_pixels_stats_async's arguments: the same, and the plane of
+// second moments.  A type of its own, so that the plain kernels' argument
+// block -- and with it their code -- stays what it was.
+struct PixelsStatsArgs : PixelsArgs {
+    float *m2;                    // 1 float per slot: the running mean of |R|^2
+};
+template <bool STATS> struct PixelsArgsOf { using type = PixelsArgs; };
+template <> struct PixelsArgsOf<true> { using type = PixelsStatsArgs; };
+
+// STATS: beside the colour the lane keeps m2, the running mean of the samples'
+// |R|^2 folded with rad_fold's own factors (rad_fold1) -- read where the
+// colour is read, stored where it is stored.  One more live float and one
+// more pointer; every other statement is the plain kernel's, so colours,
+// seeds, pixels and counts are its bits.
+template <int GEO, bool DL, bool STATS>
+__global__ void __launch_bounds__(64 * query_wpb(GEO))
+pixels_kernel(typename PixelsArgsOf<STATS>::type a, BvhView bvh)
 {
     extern __shared__ __attribute__((aligned(16))) char rmem[];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), wpb = (int)(blockDim.x >> 6);
@@ -152,6 +167,7 @@ __global__ void __launch_bounds__(64 * query_wpb(GEO)) pixels_kernel(PixelsArgs 
     bool need_cam = false;                                      // the lane's next sample has no ray yet
     uint32_t s0 = 0, s1 = 0;
     v3 col = mk(0.f, 0.f, 0.f);
+    float m2 = 0.f;                                             // (STATS)
     RadPath P;
     P.nl = P.lsum = mk(0.f, 0.f, 0.f);
     P.lmax = P.lw = 0.f;
@@ -170,6 +186,7 @@ __global__ void __launch_bounds__(64 * query_wpb(GEO)) pixels_kernel(PixelsArgs 
                 a.seeds_out[2 * i] = s0;
                 a.seeds_out[2 * i + 1] = s1;
                 if (a.done) a.done[i] = kend;
+                if constexpr (STATS) a.m2[i] = m2;
                 k = kend = 0;
             }
             if (exhausted) break;
@@ -201,6 +218,7 @@ __global__ void __launch_bounds__(64 * query_wpb(GEO)) pixels_kernel(PixelsArgs 
                             s1 = r1;
                             col = mk(0.f, 0.f, 0.f);
                             if (base > 0) col = mk(a.colors[3 * i], a.colors[3 * i + 1], a.colors[3 * i + 2]);
+                            if constexpr (STATS) m2 = base > 0 ? a.m2[i] : 0.f;
                             k = base;
                             kend = base + t;
                             need_cam = true;
@@ -233,6 +251,7 @@ __global__ void __launch_bounds__(64 * query_wpb(GEO)) pixels_kernel(PixelsArgs 
                 need_cam = false;
             } else {
                 rad_fold(col, mk(0.f, 0.f, 0.f), k);
+                if constexpr (STATS) rad_fold1(m2, 0.f, k);
                 k++;
                 need_cam = k < kend;
             }
@@ -264,6 +283,7 @@ __global__ void __launch_bounds__(64 * query_wpb(GEO)) pixels_kernel(PixelsArgs 
                 next = rad_diffuse<DL>(P, s0, s1) ? RAD_DONE : RAD_RAY;
             if (next == RAD_DONE) {
                 rad_fold(col, P.rad, k);
+                if constexpr (STATS) rad_fold1(m2, (P.rad.x * P.rad.x + P.rad.y * P.rad.y) + P.rad.z * P.rad.z, k);
                 k++;
                 need_cam = k < kend;                            // the next sample's ray: drawn above; else the lane idles
                 rad_begin(P, idle);

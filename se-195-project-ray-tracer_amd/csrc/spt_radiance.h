@@ -249,6 +249,19 @@ __device__ __forceinline__ void rad_fold(v3 &col, const v3 r, int current)
     }
 }
 
+// The same fold for one scalar with rad_fold's own k1, k2: the running mean of
+// a per-sample quantity kept beside the colour (spt_pixels.h's second moment).
+__device__ __forceinline__ void rad_fold1(float &m, const float q, int current)
+{
+    if (current == 0) {
+        m = q;
+    } else {
+        const float k1 = (float)current;
+        const float k2 = rcp_nr(k1 + 1.f);
+        m = (m * k1 + q) * k2;
+    }
+}
+
 // One query for every lane with `want` set: the nearest hit below t, or
 // (shadow) any hit below t; returns the sphere (negative: none) and the
 // distance in t.  Scan families: the loop runs with every lane (a lane

@@ -28,6 +28,7 @@ EXPORTS = ("rt_last_error", "rt_device_count", "rt_set_device", "rt_release", "r
            "spt_pack_pixels_async",
            "spt_scene_update_async", "spt_scene_update_info", "spt_scene_read_hierarchy", "spt_multi_update_scene",
            "spt_scene_query_async", "spt_scene_radiance_async", "spt_scene_render_pixels_async",
+           "spt_scene_render_pixels_stats_async", "spt_frame_plan_scratch_bytes", "spt_frame_plan_async",
            "spt_multi_create", "spt_multi_destroy", "spt_multi_set_scene", "spt_multi_bands", "spt_multi_upload",
            "spt_multi_render_async", "spt_multi_gather_async", "spt_multi_sync", "spt_multi_download",
            "spt_multi_read_frame", "spt_multi_counters", "spt_multi_band_buffers", "spt_render_multi",
@@ -63,6 +64,12 @@ class Sphere(C.Structure):
 class Camera(C.Structure):
     """smallptgpu-v1.6/camera.h:29-34 (60 bytes)."""
     _fields_ = [("orig", Vec3), ("target", Vec3), ("dir", Vec3), ("x", Vec3), ("y", Vec3)]
+
+
+class PlanParams(C.Structure):
+    """include/rt_hip.h spt_plan_params (20 bytes)."""
+    _fields_ = [("min_samples", C.c_int32), ("max_samples", C.c_int32), ("step", C.c_int32), ("tol", C.c_float),
+                ("floor", C.c_float)]
 
 
 class Float4(C.Structure):
@@ -135,6 +142,13 @@ def lib():
         L.spt_scene_radiance_async.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, i, i, i, vp]
     if hasattr(L, "spt_scene_render_pixels_async"):
         L.spt_scene_render_pixels_async.argtypes = [vp, vp, vp, vp, vp, vp, i, i, vp, vp, C.c_size_t, i, vp, i, i, vp]
+    if hasattr(L, "spt_scene_render_pixels_stats_async"):
+        L.spt_scene_render_pixels_stats_async.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, vp, vp, C.c_size_t, i, vp, i,
+                                                          i, vp]
+    if hasattr(L, "spt_frame_plan_async"):
+        L.spt_frame_plan_scratch_bytes.argtypes = [i, i]
+        L.spt_frame_plan_scratch_bytes.restype = C.c_size_t
+        L.spt_frame_plan_async.argtypes = [vp, vp, vp, i, i, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]
     if hasattr(L, "spt_multi_create"):
         ip = C.POINTER(C.c_int)
         L.spt_multi_create.argtypes = [vp, u, i, i, vp, i, C.POINTER(vp)]

@@ -2,7 +2,8 @@
 buffers, launched asynchronously -- the path the GPU tests and the tools
 drive.  This module is the one place in the package that spells out the calls
 to spt_scene_render_async, spt_scene_render_groups_async,
-spt_scene_render_list_async and spt_scene_render_pixels_async
+spt_scene_render_list_async, spt_scene_render_pixels_async,
+spt_scene_render_pixels_stats_async and spt_frame_plan_async
 (include/rt_hip.h).
 
 torch is imported inside the functions, so `import rtamd` works without it.
@@ -12,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import scenes
-from ._lib import SPT_PATH_TRACING, check as _check, entry, lib
+from ._lib import SPT_PATH_TRACING, PlanParams, check as _check, entry, lib
 
 
 def _i32(v):
@@ -38,6 +39,39 @@ class SmallptDeviceFrame:
         self.pixels = torch.zeros(w * h, dtype=torch.int32, device=self.device)
         self.counters = torch.zeros(4, dtype=torch.int64, device=self.device)
         self._done = None
+        self._m2 = None
+        self._plan = {}                     # cap -> (pixels, take): frame.plan()'s lists
+        self._plan_scratch = None
+        self._plan_totals = None
+        self._error = None
+
+    @property
+    def m2(self):
+        """The running mean of the samples' |R|^2 per pixel, float32 [w * h]
+        in slot order like `done` (render_pixels(stats=True) keeps it beside
+        the colour); made, zeroed, at its first use."""
+        if self._m2 is None:
+            import torch
+            self._m2 = torch.zeros(self.w * self.h, dtype=torch.float32, device=self.device)
+        return self._m2
+
+    @property
+    def plan_totals(self):
+        """int64 [2] on the device: the pixels the last plan() listed (before
+        truncation at its cap) and the sum of their takes."""
+        if self._plan_totals is None:
+            import torch
+            self._plan_totals = torch.zeros(2, dtype=torch.int64, device=self.device)
+        return self._plan_totals
+
+    @property
+    def error(self):
+        """float32 [w * h] in slot order: every pixel's relative standard
+        error as the last plan(error=True) saw it (+inf below min_samples)."""
+        if self._error is None:
+            import torch
+            self._error = torch.zeros(self.w * self.h, dtype=torch.float32, device=self.device)
+        return self._error
 
     @property
     def done(self):
@@ -114,7 +148,7 @@ class SmallptDeviceFrame:
         return _check(rc) if check else rc
 
     def render_pixels(self, pixels, take=None, nsamples=0, *, use_done=True, first_sample=0, mode=SPT_PATH_TRACING,
-                      seeds_in=None, stream=None, check=True):
+                      seeds_in=None, stream=None, check=True, stats=False):
         """One asynchronous launch (spt_scene_render_pixels_async) that adds
         samples to the listed pixels only: `pixels` is a contiguous int32
         device tensor of indices y * w + x (the index of `self.pixels`; an
@@ -126,10 +160,12 @@ class SmallptDeviceFrame:
         first_sample, as render() does.  seeds_in defaults to self.seeds with
         use_done (a progressive loop: start it with
         frame.seeds.copy_(frame.seeds0)), else to seeds0, as for render().
+        stats=True (spt_scene_render_pixels_stats_async) also keeps self.m2,
+        the running mean of the samples' |R|^2, and changes no other bit.
         Unlisted pixels are not touched in any buffer.  Returns the entry
         point's code (raises RTError on failure unless check=False).
-        Allocates nothing on the device (but self.done at its first use) and
-        never synchronises."""
+        Allocates nothing on the device (but self.done and self.m2 at their
+        first use) and never synchronises."""
         import torch
 
         def is_list(x):
@@ -155,10 +191,67 @@ class SmallptDeviceFrame:
         d_take = None if take is None else (take.data_ptr() if nlist else self.pixels.data_ptr())
         d_done = self.done.data_ptr() if use_done else None
         stream = getattr(stream, "cuda_stream", stream)
-        rc = entry("spt_scene_render_pixels_async")(
-            scene, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h, d_list, d_take, nlist, nsamples,
-            d_done, first_sample, mode, stream)
+        if stats:
+            d_m2 = self.m2.data_ptr()
+            rc = entry("spt_scene_render_pixels_stats_async")(
+                scene, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, d_m2, w, h, d_list, d_take, nlist, nsamples,
+                d_done, first_sample, mode, stream)
+        else:
+            rc = entry("spt_scene_render_pixels_async")(
+                scene, camera, d_colors, d_seeds_in, d_seeds_out, d_pixels, w, h, d_list, d_take, nlist, nsamples,
+                d_done, first_sample, mode, stream)
         return _check(rc) if check else rc
+
+    def plan(self, tol, min_samples, max_samples, step, floor=1e-3, cap=None, error=False, *, stream=None,
+             check=True):
+        """The next pixel list, built on the device (spt_frame_plan_async)
+        from colors, m2 and done: a pixel below min_samples is brought up to
+        it; one whose relative standard error sqrt(max(m2 - |c|^2, 0) /
+        (done * (|c|^2 + floor))) is above tol takes `step` more, never past
+        max_samples.  Returns the frame-owned (pixels, take) int32 tensors of
+        length cap (default w * h; made at the first call with that cap and
+        reused): the listed pixels in 8 x 8 tile order, then -1 / 0 padding, so
+        render_pixels takes them as they are.  Fills self.plan_totals and,
+        with error=True, self.error.  Asynchronous on `stream` (default:
+        torch's current one); after the buffers' first use it allocates
+        nothing and never synchronises, so (plan, render_pixels) pairs may be
+        enqueued back to back or captured."""
+        import torch
+        cap = self.w * self.h if cap is None else int(cap)
+        if cap < 0:
+            raise ValueError("plan: negative cap")
+        if cap not in self._plan:
+            self._plan[cap] = (torch.full((cap,), -1, dtype=torch.int32, device=self.device),
+                               torch.zeros(cap, dtype=torch.int32, device=self.device))
+        if self._plan_scratch is None:
+            nbytes = entry("spt_frame_plan_scratch_bytes")(self.w, self.h)
+            self._plan_scratch = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=self.device)
+        pixels, take = self._plan[cap]
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        stream = getattr(stream, "cuda_stream", stream)
+        params = PlanParams(min_samples, max_samples, step, tol, floor)
+        # (d_colors, d_m2, d_done, w, h, params, d_list, d_take, cap, d_error, d_totals, d_scratch, stream)
+        rc = entry("spt_frame_plan_async")(
+            self.colors.data_ptr(), self.m2.data_ptr(), self.done.data_ptr(), self.w, self.h, C.byref(params),
+            pixels.data_ptr() if cap else None, take.data_ptr() if cap else None, cap,
+            self.error.data_ptr() if error else None, self.plan_totals.data_ptr(), self._plan_scratch.data_ptr(),
+            stream)
+        if check:
+            _check(rc)
+        return pixels, take
+
+    def refine(self, passes, *, mode=SPT_PATH_TRACING, stream=None, **params):
+        """`passes` x (plan(**params), render_pixels(stats=True,
+        use_done=True)) on one stream with no synchronisation in between: the
+        closed loop of adaptive sampling.  A pass whose plan lists nothing
+        renders nothing; self.plan_totals tells the caller, when it wants to
+        know, whether the last plan was empty.  Start a frame with reset() and
+        seeds.copy_(seeds0)."""
+        for _ in range(passes):
+            pixels, take = self.plan(stream=stream, **params)
+            self.render_pixels(pixels, take, mode=mode, stream=stream, stats=True)
+        return self
 
     def budget_list(self, budget, order="tile"):
         """(pixels, take) for render_pixels from an h x w integer budget map
@@ -188,13 +281,15 @@ class SmallptDeviceFrame:
 
     def reset(self, colors=0.0, pixels=0, seeds=0):
         """Refills the output tensors in place (pixels and seeds take a 32-bit
-        pattern) and zeroes the counters (and `done`, where it exists)."""
+        pattern) and zeroes the counters (and `done` and `m2`, where they exist)."""
         self.colors.fill_(colors)
         self.pixels.fill_(_i32(pixels))
         self.seeds.fill_(_i32(seeds))
         self.counters.zero_()
         if self._done is not None:
             self._done.zero_()
+        if self._m2 is not None:
+            self._m2.zero_()
         return self
 
     def host(self):
