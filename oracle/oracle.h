@@ -14,7 +14,8 @@
  *
  * Parity pin: SURVEY.md §8(c) known-answer hashes produced by the reference
  * itself (tests/golden/known_answers.json) plus oracle/_ref builds of the
- * reference sources that compile without stand-ins (see oracle/Makefile).
+ * reference sources, unmodified and in place (see oracle/Makefile; the Whitted
+ * engine needs two empty Windows headers, its OpenCL kernel a host shim).
  *
  * Struct layouts are byte-identical to the reference's:
  *   Primitive 96 B  raytracer.h:23-32 (+ Material :18-21, plane common.h:49-53)

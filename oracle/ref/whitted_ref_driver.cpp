@@ -1,14 +1,21 @@
 /*
  * oracle/ref/whitted_ref_driver.cpp -- TEST INFRASTRUCTURE ONLY.
  *
- * Links the reference's own raytracer3.0.06.no_rec.samp/scene.cpp (compiled
- * unmodified from /root/reference) into oracle/_ref/libref_whitted_scene.so,
- * exposing Scene_InitScene / Primitive_Intersect / Primitive_GetNormal so the
- * C restatement in oracle/whitted_oracle.c can be checked against them.
- * raytracer.cpp (Engine_Raytrace / Engine_Render) includes <windows.h>, which
- * this image lacks: it is not built (no stand-in headers); the full-frame pin
- * for the Whitted path is the reference-produced known-answer hashes of
- * SURVEY.md §8(c) (tests/golden/known_answers.json).
+ * Links the reference's own raytracer3.0.06.no_rec.samp/raytracer.cpp,
+ * scene.cpp and surface.cpp (compiled unmodified, where they lie) into
+ * oracle/_ref/libref_whitted_scene.so, so the C restatement in
+ * oracle/whitted_oracle.c can be checked against them:
+ *   - Scene_InitScene / Primitive_Intersect / Primitive_GetNormal, one call
+ *     at a time;
+ *   - ref_whitted_render: Engine_InitRender + Engine_Render (which call
+ *     Engine_Raytrace) on the caller's primitives at any frame size -- the
+ *     whole-frame pin of orw_render.
+ * raytracer.cpp includes "windows.h" and "winbase.h" and uses nothing from
+ * them: the build puts oracle/ref/win_stub, two empty headers of this
+ * repository's own, first on the include path.  The engine's state is global
+ * and it is single-threaded: one frame at a time.
+ * The OpenCL kernel's twin, ref_whitted_render_ocl, is in
+ * whitted_ocl_ref_driver.cpp.
  */
 #include <string.h>
 #include "common.h"
@@ -41,3 +48,19 @@ extern "C" void ref_primitive_normal(const Primitive *p, const float pos[3], flo
 }
 
 extern "C" int ref_sizeof_primitive(void) { return (int)sizeof(Primitive); }
+
+/* testapp.cpp's launch sequence with the scene replaced by the caller's
+ * array: writes rows [20, h - 70) of dest (w * h pixels), nothing else. */
+extern "C" void ref_whitted_render(Primitive *prims, int n, Pixel *dest, int w, int h)
+{
+    Scene *saved = m_Scene;
+    Engine_Constructor();
+    m_Scene->m_Primitive = prims;
+    m_Scene->m_Primitives = n;
+    TracedRays_init();
+    Engine_SetTarget(dest, w, h);
+    Engine_InitRender();
+    Engine_Render();
+    free(m_Scene);
+    m_Scene = saved;
+}

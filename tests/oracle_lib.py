@@ -267,7 +267,52 @@ def ref_queue_render(Q, w, h, prims, n):
     px = np.zeros((h, w, 4), dtype=np.uint8)
     Q.ref_q_render(px.ctypes.data, w, h, prims, n)
     return px
+
+
+def _ref_whitted_frame(entry, w, h, prims, n):
+    """A zero-cleared uint32 [h, w] frame rendered by the reference build's
+    `entry` (oracle/_ref/libref_whitted_scene.so), or None where the library
+    or the entry is absent.  prims: a 96-byte Primitive array (this module's
+    or the product binding's), default the reference scene."""
+    libs = ref_libs()
+    if libs is None or not hasattr(libs[0], entry):
+        return None
+    if prims is None:
+        prims, n = whitted_scene()
+    assert C.sizeof(prims) >= 96 * n
+    frame = np.zeros((h, w), dtype=np.uint32)
+    fn = getattr(libs[0], entry)
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    fn.restype = None
+    fn(C.addressof(prims), n, frame.ctypes.data, w, h)
+    return frame
+
+
+def ref_whitted_render(w, h, prims=None, n=None):
+    """The reference's own Engine_InitRender + Engine_Render (raytracer.cpp
+    compiled unmodified): rows [20, h - 70) of a zero frame.  None without
+    oracle/_ref.  Single-threaded, global state."""
+    return _ref_whitted_frame("ref_whitted_render", w, h, prims, n)
+
+
+def ref_whitted_render_ocl(w, h, prims=None, n=None):
+    """The reference's raytrace_kernel (openCLcode.cl compiled as host C++,
+    built-ins as glibc's sqrtf / expf / powf), one call per work-item: rows
+    [20, min(530, h)) of a zero frame.  None without oracle/_ref."""
+    return _ref_whitted_frame("ref_whitted_render_ocl", w, h, prims, n)
+
+
+_ref_libs = False
+
+
 def ref_libs():
+    global _ref_libs
+    if _ref_libs is False:
+        _ref_libs = _load_ref_libs()
+    return _ref_libs
+
+
+def _load_ref_libs():
     """(whitted_scene_lib, smallpt_lib) built from /root/reference, or None."""
     d = os.path.join(ORACLE_DIR, "_ref")
     w = os.path.join(d, "libref_whitted_scene.so")

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import lit_scenes as L
 import oracle_lib as O
 from test_oracle_queue import KA, random_scene
 
@@ -51,6 +52,46 @@ def test_random_scenes(rt, seed):
     assert (px == ref).all()
     assert cnt == rc
     assert (rt.queue_render(96, 72, P, n) == ref).all()
+
+
+def _lit_vs_oracle(rt, seed):
+    """A lit closed-room scene (lit_scenes.queue_lit): the oracle's frame must
+    meet the lit-scene conditions, then the counted and the uncounted kernels
+    must reproduce it, and the counted ones its counters."""
+    P, n, ref, rc = L.queue_lit(seed)
+    L.check_lit(ref)
+    px, cnt = rt.queue_render(L.QUEUE_W, L.QUEUE_H, P, n, counters=True)
+    bad = np.argwhere((px != ref).any(-1))
+    assert bad.size == 0, "%d pixels differ, first at %s (got %s want %s)" % (
+        len(bad), bad[0].tolist(), px[tuple(bad[0])].tolist(), ref[tuple(bad[0])].tolist())
+    assert cnt == rc
+    assert (rt.queue_render(L.QUEUE_W, L.QUEUE_H, P, n) == ref).all()
+
+
+@pytest.mark.parametrize("seed", L.QUEUE_SEEDS)
+def test_lit_random_scenes(rt, seed):
+    """test_random_scenes' closed rooms re-drawn until the frame is lit: at
+    least a quarter of the pixels non-black and 100 distinct values (half of
+    test_random_scenes' own frames are one flat value, where only the counters
+    can tell kernels apart)."""
+    _lit_vs_oracle(rt, seed)
+
+
+def test_lit_scene_exact_path_everywhere(rt, monkeypatch):
+    """RT_QUEUE_EXACT_ALL=1 (every specular term finished by fix_kernel) on a
+    lit scene with the camera inside a glass sphere."""
+    monkeypatch.setenv("RT_QUEUE_EXACT_ALL", "1")
+    assert L.queue_features(*L.queue_lit(L.QUEUE_EXACT_SEED)[:2])["camera_inside"]
+    _lit_vs_oracle(rt, L.QUEUE_EXACT_SEED)
+
+
+def test_lit_scene_pool_overflow(rt, monkeypatch):
+    """RT_QUEUE_POOL_CAP=4096 on a lit scene with over a hundred times as
+    many rays as the pool has records: the trees whose nodes did not fit are
+    re-evaluated by final_kernel and carry colour."""
+    monkeypatch.setenv("RT_QUEUE_POOL_CAP", "4096")
+    assert L.queue_lit(L.QUEUE_POOL_SEED)[3][0] > 100 * 4096
+    _lit_vs_oracle(rt, L.QUEUE_POOL_SEED)
 
 
 def test_max_primitives(rt):

@@ -6,6 +6,7 @@ the integer pixels and RNG state must match exactly."""
 import numpy as np
 import pytest
 
+import lit_scenes as L
 from spt_check import assert_same, golden, oracle_frame as _oracle_frame
 
 pytestmark = pytest.mark.gpu
@@ -458,6 +459,27 @@ def test_random_scenes_vs_oracle(rt, oracle, seed):
         g.render(k, counters=False)
     assert (g.colors.view(np.uint32) == f.colors.view(np.uint32)).all()
     assert (g.seeds == f.seeds).all() and (g.pixels == f.pixels).all()
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("seed", L.ROOM_SEEDS)
+def test_room_scenes_vs_oracle(rt, seed, mode):
+    """Closed rooms (lit_scenes.smallpt_room: Cornell's walls recoloured, some
+    mirrors, 1-3 emitters and up to 29 diffuse / mirror / glass spheres, the
+    camera inside) whose oracle frames are at least a quarter lit with 100 or
+    more distinct pixels -- test_random_scenes_vs_oracle's cameras mostly look
+    into the void.  The same checks as that test: split progressive passes,
+    counted and uncounted kernels, all bit for bit, under both estimators."""
+    S, n, cam, w, h, steps, ref = L.room_oracle(seed, mode)
+    L.check_lit(ref[2])
+    f = rt.SmallptFrame(w, h, spheres=S, nspheres=n, camera=cam, mode=mode)
+    for k in steps:
+        f.render(k)
+    _check((f.colors, f.seeds, f.pixels, f.counters), ref)
+    g = rt.SmallptFrame(w, h, spheres=S, nspheres=n, camera=cam, mode=mode)
+    for k in steps:
+        g.render(k, counters=False)
+    assert_same(g, ref, counted=False)
 
 
 @pytest.mark.parametrize("geo", ["lds", "global"])

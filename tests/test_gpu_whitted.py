@@ -4,6 +4,8 @@ Bar: bit-exact uint32 frames, identical ray / test / TIR counts."""
 import numpy as np
 import pytest
 
+import lit_scenes as L
+
 pytestmark = pytest.mark.gpu
 
 
@@ -114,6 +116,48 @@ def test_random_scenes_vs_oracle(rt, oracle, seed):
     ref, rc = oracle.whitted_render_ocl(w, h, nthreads=8, prims=P, n=n)
     got, gc = rt.whitted_render_ocl(w, h, prims=P, nprims=n, counters=True)
     assert (got == ref).all() and gc == rc
+
+
+def _walled_vs_oracle(rt, seed):
+    """A lit walled scene (lit_scenes.whitted_walled) under both semantics:
+    the oracle's frames must meet the lit-scene conditions before the
+    kernel's frames and counters are compared with them, bit for bit."""
+    P, n, w, h, (ref, rc), (oref, orc) = L.walled_oracle(seed)
+    wc, wo = L.whitted_windows(w, h)
+    L.check_lit(ref, wc[:2])
+    L.check_lit(oref, wo[:2])
+    got, gc = rt.whitted_render(w, h, prims=P, nprims=n, counters=True)
+    diff = np.argwhere(got != ref)
+    assert diff.size == 0, "%d pixels differ, first at %s (got %x want %x)" % (
+        len(diff), diff[0].tolist(), got[tuple(diff[0])], ref[tuple(diff[0])])
+    assert gc == rc, (gc, rc)
+    got, gc = rt.whitted_render_ocl(w, h, prims=P, nprims=n, counters=True)
+    diff = np.argwhere(got != oref)
+    assert diff.size == 0, "OpenCL semantics: %d pixels differ, first at %s (got %x want %x)" % (
+        len(diff), diff[0].tolist(), got[tuple(diff[0])], oref[tuple(diff[0])])
+    assert gc == orc, (gc, orc)
+    return rc, w, wc
+
+
+@pytest.mark.parametrize("seed", L.WALLED_SEEDS)
+def test_walled_scenes_vs_oracle(rt, seed):
+    """Random scenes built so that light reaches the camera (walls that keep
+    every sphere, light and the camera on their normal's side; glass, mirrors,
+    nested glass, mirror walls, a wall flagged as a light, 64 primitives):
+    25 % or more of each frame is lit with hundreds of distinct values, so
+    the diffuse, specular, reflection and Beer's-law arithmetic all reach
+    pixels -- unlike test_random_scenes_vs_oracle's mostly black frames."""
+    _walled_vs_oracle(rt, seed)
+
+
+def test_walled_deep_trees_through_fixup_and_slabs(rt, monkeypatch):
+    """The deepest-tree walled scene with child queues of 1000 items and
+    three interleaved slabs: most trees finish in the sequential fixup pass
+    and the slab interleave carries real colour."""
+    monkeypatch.setenv("RT_WHITTED_QUEUE_CAP", "1000")
+    monkeypatch.setenv("RT_WHITTED_SLABS", "3")
+    rc, w, wc = _walled_vs_oracle(rt, L.WALLED_DEEP_SEED)
+    assert L.rays_per_primary(rc, w, wc) > 3.0
 
 
 @pytest.mark.parametrize("streams", ["1", "2"])
