@@ -234,7 +234,13 @@ int spt_scene_info(const spt_scene *scene, int *out, int nout);
  * (one small upload).  Scheduling only -- results are identical; during
  * stream capture the learnt order is used but not updated.  A scene's order
  * is updated by the calling thread: render one scene from one host thread
- * at a time.  Hierarchy scenes give every launch one of 64 work-counter
+ * at a time.  That thread may have launches of the scene in flight on
+ * several streams at once: the library orders the scene's own state (the
+ * learnt order and the work counters) across them -- a new order never
+ * lands in a buffer a running launch dispatches from, a counter entry is
+ * not handed out again while its launch runs -- without blocking the host
+ * and without allocating.  The caller's buffers stay the caller's to order.
+ * Hierarchy scenes give every launch one of 64 work-counter
  * entries; a launch captured into a graph keeps its entry for the graph's
  * life (the graph may be replayed at any time), so at most 64 captured
  * launches of one scene can exist -- the next capture fails RT_ERR_INVALID

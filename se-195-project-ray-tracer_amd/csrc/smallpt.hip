@@ -1786,6 +1786,7 @@ int launch(const spt_scene &sc, const RenderCall &c, const Shape &g)
                        gl, sc.nlights, sc.bvh, c.counters, work, v.persist() ? sptpolicy::split_word(g, t) : 0,
                        sptpolicy::pack_nheavy(t.n1, t.n2),
                        sptpolicy::pack_sflags(sc.no_refr, g.cost_max, v.dq() ? sptpolicy::sq_threshold(g.tune.sq) : 0));
+    if (work) sptsched::work_launched(sc.work, work, c.stream);
     return RT_OK;
 }
 
@@ -1835,7 +1836,7 @@ int build_scene_bvh(spt_scene *sc, const rt_sphere *spheres)
     if (e == hipSuccess && wide) e = hipMemcpy(base + w_off, wb.words.data(), w_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess && wide)
         e = hipMemcpy(base + w_off + w_bytes, wb.maxid.data(), m_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && wide) e = hipMalloc(&sc->work.d, 4 * sizeof(int) * sptsched::WorkRing::N);
+    if (e == hipSuccess && wide) e = sptsched::ring_create(sc->work);
     if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_create hierarchy upload");
     rt::smallpt::BvhView &v = sc->bvh;
     v.node = (const float4 *)base;
@@ -1941,7 +1942,7 @@ extern "C" int spt_scene_destroy(spt_scene *sc)
     if (sc->d_spheres) (void)hipFree(sc->d_spheres);
     if (sc->d_soa) (void)hipFree(sc->d_soa);
     if (sc->d_bvh) (void)hipFree(sc->d_bvh);
-    if (sc->work.d) (void)hipFree(sc->work.d);
+    sptsched::ring_release(sc->work);
     sptsched::sched_release(sc->sched);
     sptsched::sched_release(sc->sched_cnt);
     delete sc;
@@ -1963,7 +1964,7 @@ extern "C" int spt_scene_release_captures(const spt_scene *sc)
 {
     if (!sc) return rtrt::fail(RT_ERR_INVALID, "spt_scene_release_captures: null scene");
     std::lock_guard<std::mutex> lk(sc->work.mu);
-    sc->work.captured = 0;
+    sc->work.book.captured = 0;
     return RT_OK;
 }
 
@@ -2444,6 +2445,7 @@ int scene_render(const spt_scene *sc, const RenderCall &c)
                                          c.mode & ~(SPT_COUNT_RAYS | SPT_COST_MAX), grid.nslots, *c.cam});
     }
     int rc = launch(*sc, c, grid);
+    if (!c.list && sc->bvh.node) sptsched::sched_used(sched, c.stream);
     if (rc == RT_OK) rc = rtrt::check_launch("spt render_kernel");
     if (rc == RT_OK && record) sptsched::sched_after(sched, c.stream);
     return rc;
