@@ -123,7 +123,9 @@ int rtw_render_async(const rt_primitive *d_prims, int nprims, uint32_t *d_xrgb, 
  * [20, min(530, h)) (openCLcode.cl:66-67), SX = WX1 + x*DX per pixel (:22-23),
  * 2x2 sub-samples (:66), a light hit adds the light's colour
  * (openCLcode.h:176-182), reflection child folded before the refraction child
- * (:199-233), x(256/4) scale (:238-240).  The OpenCL built-ins (sqrt, '/',
+ * (:199-233), x(256/4) scale (:238-240), the channels ORed into the pixel
+ * (:245; the CPU path adds them), a shadow ray's occluders the primitives with
+ * m_Light < 1 (openCLcode.h:235; the CPU path: == 0).  The OpenCL built-ins (sqrt, '/',
  * exp, pow) are computed as the CPU path's correctly rounded / glibc
  * functions.  Same counters as rtw_render.  Rows outside the window are not
  * written. */

@@ -185,7 +185,9 @@ static int engine_raytrace(const or_primitive *P, int n, const ray_t *a_ray, vec
             r.d = L;
             cnt->shadow++;
             for (int s = 0; s < n; s++) {
-                if (P[s].m_Light == 0) {
+                /* raytracer.cpp:100 'm_Light==0', openCLcode.h:235 'm_Light<1':
+                 * a negative flag occludes only under the OpenCL semantics */
+                if (ocl ? P[s].m_Light < 1 : P[s].m_Light == 0) {
                     cnt->tests++;
                     if (prim_intersect(&P[s], &r, &tdist)) { shade = 0; break; }
                 }
@@ -383,7 +385,10 @@ static uint32_t render_pixel(const or_primitive *P, int n, float SX, float SY,
     if (red > 255) red = 255;
     if (green > 255) green = 255;
     if (blue > 255) blue = 255;
-    return (uint32_t)((red << 16) + (green << 8) + blue);
+    /* raytracer.cpp:523 adds the channels, openCLcode.cl:245 ORs them: one
+     * word for channels in [0, 255], not for a negative one. */
+    if (ocl) return ((uint32_t)red << 16) | ((uint32_t)green << 8) | (uint32_t)blue;
+    return ((uint32_t)red << 16) + ((uint32_t)green << 8) + (uint32_t)blue;
 }
 
 void orw_render(const or_primitive *P, int n, uint32_t *dest, int w, int h,

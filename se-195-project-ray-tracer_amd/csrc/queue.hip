@@ -161,15 +161,18 @@ __device__ Hit shade_hit(const Scene &S, const ray3 &ray, float dist, int prim, 
                     h.col.z += diff * hc.z * lm.z;
                 }
             }
-            // :256-275.  An occluded light adds (float)(pow * m_spec * 0.0) =
-            // +0 (pow of a dot <= ~1 is finite): only lit points evaluate pow.
-            if (pspec > 0 && shade > 0) {
+            // :256-275.  An occluded light still adds (float)(pow * m_spec *
+            // 0.0) times its colour: +0 for finite factors, NaN for an
+            // overflowing pow, an infinite m_spec or a non-finite light
+            // colour (spec20_occluded) -- only lit points evaluate pow.
+            if (pspec > 0) {
                 const float td = L.x * N.x + L.y * N.y + L.z * N.z;
                 const v3 R = mk(L.x - 2.0f * td * N.x, L.y - 2.0f * td * N.y, L.z - 2.0f * td * N.z);
                 const float dp = ray.d.x * R.x + ray.d.y * R.y + ray.d.z * R.z;
                 if (dp > 0) {
-                    // shade = 1 here: the reference's * (double)shade is exact
-                    const float spec = spec20<EXACT, UNCERT>(dp, pspec, h.amb);
+                    // shade = 1 where lit: the reference's * (double)shade is exact
+                    const float spec = shade > 0 ? spec20<EXACT, UNCERT>(dp, pspec, h.amb)
+                                                 : spec20_occluded<EXACT, UNCERT>(dp, pspec, h.amb);
                     h.col.x += spec * lm.x;
                     h.col.y += spec * lm.y;
                     h.col.z += spec * lm.z;

@@ -32,6 +32,21 @@ RTM_HD float spec20(float dp, float pspec, bool &amb)
     return lo;
 }
 
+// The same factor for a light the shadow ray found occluded: the reference
+// still evaluates (float)(pow((double)dp, 20.0) * (double)pspec * 0.0), which
+// is +0 while the product is finite and NaN once it is not (inf * 0).  For
+// 0 < dp <= 2^25 and a finite pspec > 0 the product is below 2^501 * 2^128:
+// finite, so +0 without any pow.  Everything else (a normal of length 5 and a
+// non-unit ray can give dp far above 2; m_spec may be inf) is left to the
+// exact path, like an uncertified term.
+template <bool EXACT, bool UNCERT = false>
+RTM_HD float spec20_occluded(float dp, float pspec, bool &amb)
+{
+    if (EXACT) return (float)(rtm::pow_d((double)dp, 20.0) * (double)pspec * 0.0);
+    amb |= !(dp <= 0x1p25f && pspec <= 3.40282347e38f) || UNCERT;
+    return 0.0f;
+}
+
 }  // namespace queue
 }  // namespace rt
 

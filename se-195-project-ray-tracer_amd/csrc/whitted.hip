@@ -235,14 +235,18 @@ __device__ __forceinline__ ray3 primary(int sub, float SX, float SY, float DX, f
 }
 
 // Builds the SoA scene image from the reference's 96-byte AoS primitives:
-// one wave, a lane per primitive (prims::fill_lists).
-__device__ void build_scene(Scene &S, const rt_primitive *__restrict__ src, int nprims)
+// one wave, a lane per primitive (prims::fill_lists).  The shadow loop's
+// occluders are the primitives with m_Light == 0 (raytracer.cpp:100) or,
+// under the OpenCL semantics, m_Light < 1 (openCLcode.h:235): a negative flag
+// occludes only there.
+__device__ void build_scene(Scene &S, const rt_primitive *__restrict__ src, int nprims, bool ocl)
 {
     const int p = __lane_id();
     const bool v = p < nprims;
     rt_primitive q{};
     if (v) q = src[p];
-    const int il = prims::fill_lists(S, v, q.type == SPHERE, q.type == PLANE, q.m_Light > 0, q.m_Light == 0,
+    const int il = prims::fill_lists(S, v, q.type == SPHERE, q.type == PLANE, q.m_Light > 0,
+                                     ocl ? q.m_Light < 1 : q.m_Light == 0,
                                      make_float4(q.m_Centre.x, q.m_Centre.y, q.m_Centre.z, q.m_SqRadius),
                                      make_float4(q.plane_N.x, q.plane_N.y, q.plane_N.z, q.plane_D));
     if (v) {
@@ -263,9 +267,9 @@ __device__ void build_scene(Scene &S, const rt_primitive *__restrict__ src, int 
 // first wave (replaces a one-lane scene pass and two fills).
 __global__ void __launch_bounds__(256) prep_kernel(const rt_primitive *__restrict__ src, int nprims,
                                                    Scene *__restrict__ scene, uint4 *__restrict__ z0, int n0,
-                                                   uint4 *__restrict__ z1, int n1)
+                                                   uint4 *__restrict__ z1, int n1, bool ocl)
 {
-    if (src && blockIdx.x == 0 && threadIdx.x < 64) build_scene(*scene, src, nprims);
+    if (src && blockIdx.x == 0 && threadIdx.x < 64) build_scene(*scene, src, nprims, ocl);
     prims::zero_fill(z0, n0, z1, n1);
 }
 
@@ -606,6 +610,12 @@ tir_kernel(WfArgs A, int L, const float *__restrict__ sx_tab, const float *__res
         const int4 e = A.tir[L][t];
         const int slot_self = e.x, tree = e.y, node = e.z;
         const float rin = __int_as_float(e.w);
+        // A flagged tree has lost a node (a full pool or TIR list, in an
+        // earlier launch): the search below would step over it and take an
+        // older ray than the reference's, and the level pass would trace and
+        // count a subtree the reference never sees.  Its child stays
+        // unqueued; fixup_kernel traces and counts it.
+        if (flagged(A, tree)) continue;
         ray3 r;
         bool found = false, broken = false;
         for (int j = node - 1; j >= 0 && !found && !broken; j--) {
@@ -772,7 +782,10 @@ final_kernel(WfArgs A, int row_end, uint32_t *__restrict__ out)
     if (red > 255) red = 255;
     if (green > 255) green = 255;
     if (blue > 255) blue = 255;
-    out[(size_t)y * A.w + x] = (uint32_t)((red << 16) + (green << 8) + blue);
+    // raytracer.cpp:523 adds the channels, openCLcode.cl:245 ORs them: one word
+    // for channels in [0, 255], not for a negative one.
+    const uint32_t r16 = (uint32_t)red << 16, g8 = (uint32_t)green << 8, b0 = (uint32_t)blue;
+    out[(size_t)y * A.w + x] = A.ocl ? (r16 | g8 | b0) : (r16 + g8 + b0);
 }
 
 struct NodeStore {       // per-lane private tree records (only traced nodes touched)
@@ -1143,7 +1156,7 @@ int render_async(const rt_primitive *d_prims, int nprims, uint32_t *d_xrgb, int 
         const int nz1 = rtrt::words16(sizeof(unsigned) * (((size_t)a.ntrees + 31) / 32));
         const int pblocks = std::min(1024, std::max(1, (nz0 + nz1 + 255) / 256));
         hipLaunchKernelGGL(rt::whitted::prep_kernel, dim3(pblocks), dim3(256), 0, sk, k < nstream ? d_prims : nullptr,
-                           nprims, (rt::whitted::Scene *)a.scene, (uint4 *)a.count, nz0, (uint4 *)a.fixbits, nz1);
+                           nprims, (rt::whitted::Scene *)a.scene, (uint4 *)a.count, nz0, (uint4 *)a.fixbits, nz1, ocl);
         rc = cnt ? launch_wavefront<true>(a, w, srows, row_end, d_sx, d_sy, DX, DY, cnt, sk, d_xrgb)
                  : launch_wavefront<false>(a, w, srows, row_end, d_sx, d_sy, DX, DY, cnt, sk, d_xrgb);
         if (rc) return frame.bail(rc);

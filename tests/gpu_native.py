@@ -11,6 +11,7 @@ HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native")
 # (name, fn id, lo, hi) float-bit ranges: the hot path's input domains.
 DOMAINS = [
     ("powf_y20", 0, 0x00000000, 0x40000000),     # raytracer.cpp:165, dot in (0, 2]
+    ("powf_y20_above2", 0, 0x40000001, 0x7f800000),   # the same with a non-unit normal: any dot > 0, +inf too
     ("powf_gamma", 1, 0x00000000, 0x3f800000),   # vec.h:62, [0, 1]
     ("powf_gamma_negzero", 1, 0x80000000, 0x80000000),
     ("expf_all", 2, 0x00000000, 0xffffffff),     # raytracer.cpp:487-489
@@ -157,7 +158,9 @@ def spec20_check(pspec_bits, lo=0x00000001, hi=0x40000000):
     patterns).  Per pspec bits: a dict of `wrong` (certified but different:
     count, inputs), `uncertified` (count, inputs), `uncertified_hi` (the count
     at or above 0x3c000000) and `host_uncertified` (count, inputs: the same
-    certificate run on the host).  Input lists hold at most spec20 cap entries."""
+    certificate run on the host).  Input lists hold at most spec20 cap
+    entries: all of them, ascending, while the count is within the cap; past
+    it the host's are the smallest and the device's any."""
     L = lib()
     cap, n = L.gmc_spec20_cap(), len(pspec_bits)
     ps = np.array(pspec_bits, np.uint32).view(np.float32)

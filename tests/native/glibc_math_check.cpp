@@ -6,7 +6,9 @@
 // pspec values to check rt_spec20.h's rounding certificate with: one more
 // line per pspec, "spec20_<pspec bits> checked certified_but_wrong
 // first_wrong_input uncertified uncertified_at_or_above_0x3c000000
-// [uncertified inputs, ascending, at most 256]".
+// [uncertified inputs, ascending, at most 256]" for dp in (0, 2], and (not
+// with "quick") one "spec20above2_<pspec bits> ..." line per pspec > 0 for dp
+// in (2, +inf].
 #include <math.h>
 #include <stdio.h>
 #include <stdint.h>
@@ -88,53 +90,82 @@ int main(int argc, char **argv)
         printf("pow_d_y20 %llu %llu 0x%08llx\n", (unsigned long long)hi, bad, first == ~0ull ? 0ull : first);
         fflush(stdout);
     }
+    // The same two above 2 (the kernels call them with any dot > 0: a normal
+    // of length 5 gives dots far above 2): every float in (2, +inf].
+    if (!quick) {
+        run("powf_y20_above2", 0x40000001u, 0x7f800000u, [](float x) { return rtm::powf(x, 20.0f); },
+            [](float x) { return ::powf(x, 20.0f); });
+        const uint32_t lo = 0x40000001u, hi = 0x7f800000u;
+        unsigned long long bad = 0, first = ~0ull;
+#pragma omp parallel for schedule(static, 1 << 16) reduction(+ : bad) reduction(min : first)
+        for (uint64_t u = lo; u <= hi; u++) {
+            const double x = (double)rtm::u2f((uint32_t)u);
+            if (rtm::d2u(rtm::pow_d(x, 20.0)) != rtm::d2u(::pow(x, 20.0))) { bad++; if (u < first) first = u; }
+        }
+        printf("pow_d_y20_above2 %llu %llu 0x%08llx\n", (unsigned long long)(hi - lo + 1), bad,
+               first == ~0ull ? 0ull : first);
+        fflush(stdout);
+    }
     // rt::queue::spec20<false> (queue.hip's specular factor: x^20 in five
     // multiplies and a rounding certificate) against what it stands for,
-    // (float)(pow((double)dp, 20.0) * (double)pspec) with the host's pow, for
-    // every float dp in (0, 2]: a certified result must be that float.
+    // (float)(pow((double)dp, 20.0) * (double)pspec) with the host's pow: a
+    // certified result must be that float.  Two sweeps: every float dp in
+    // (0, 2] with every pspec ("spec20_"), and every float dp in (2, +inf]
+    // with every pspec > 0 ("spec20above2_": queue.hip evaluates the factor
+    // only where m_spec > 0, and 0 * an overflowed x^20 is a NaN the
+    // certificate hands to the exact path).  Per pspec the uncertified inputs
+    // are counted; the 256 smallest are listed.
     {
         std::vector<float> ps;
         for (int a = 1; a < argc; a++)
             if (!strncmp(argv[a], "0x", 2)) ps.push_back(rtm::u2f((uint32_t)strtoul(argv[a], nullptr, 16)));
-        const int np = (int)ps.size();
-        const uint32_t hi = step_hi;
-        std::vector<unsigned long long> wrong(np, 0), first(np, ~0ull), unc_hi(np, 0);
-        std::vector<std::vector<uint32_t>> unc(np);
+        const auto sweep = [&](const char *label, uint32_t lo, uint32_t hi, bool positive_only) {
+            std::vector<float> pv;
+            for (float v : ps)
+                if (!positive_only || v > 0) pv.push_back(v);
+            const int np = (int)pv.size();
+            const size_t KEEP = 256;
+            std::vector<unsigned long long> wrong(np, 0), first(np, ~0ull), unc_n(np, 0), unc_hi(np, 0);
+            std::vector<std::vector<uint32_t>> unc(np);
 #pragma omp parallel
-        {
-            std::vector<unsigned long long> w(np, 0), f(np, ~0ull), uh(np, 0);
-            std::vector<std::vector<uint32_t>> un(np);
+            {
+                std::vector<unsigned long long> w(np, 0), f(np, ~0ull), un_n(np, 0), uh(np, 0);
+                std::vector<std::vector<uint32_t>> un(np);      // this thread's KEEP smallest (u ascends per thread)
 #pragma omp for schedule(static, 1 << 16) nowait
-            for (uint64_t u = 1; u <= hi; u++) {
-                const float dp = rtm::u2f((uint32_t)u);
-                const double p = ::pow((double)dp, 20.0);
-                for (int j = 0; j < np; j++) {
-                    bool amb = false;
-                    const float fast = rt::queue::spec20<false>(dp, ps[j], amb);
-                    if (amb) {
-                        un[j].push_back((uint32_t)u);
-                        if (u >= 0x3c000000u) uh[j]++;
-                    } else if (rtm::f2u(fast) != rtm::f2u((float)(p * (double)ps[j]))) {
-                        w[j]++;
-                        if (u < f[j]) f[j] = u;
+                for (uint64_t u = lo; u <= hi; u++) {
+                    const float dp = rtm::u2f((uint32_t)u);
+                    const double p = ::pow((double)dp, 20.0);
+                    for (int j = 0; j < np; j++) {
+                        bool amb = false;
+                        const float fast = rt::queue::spec20<false>(dp, pv[j], amb);
+                        if (amb) {
+                            un_n[j]++;
+                            if (un[j].size() < KEEP) un[j].push_back((uint32_t)u);
+                            if (u >= 0x3c000000u) uh[j]++;
+                        } else if (rtm::f2u(fast) != rtm::f2u((float)(p * (double)pv[j]))) {
+                            w[j]++;
+                            if (u < f[j]) f[j] = u;
+                        }
                     }
                 }
-            }
 #pragma omp critical
-            for (int j = 0; j < np; j++) {
-                wrong[j] += w[j]; unc_hi[j] += uh[j];
-                if (f[j] < first[j]) first[j] = f[j];
-                unc[j].insert(unc[j].end(), un[j].begin(), un[j].end());
+                for (int j = 0; j < np; j++) {
+                    wrong[j] += w[j]; unc_n[j] += un_n[j]; unc_hi[j] += uh[j];
+                    if (f[j] < first[j]) first[j] = f[j];
+                    unc[j].insert(unc[j].end(), un[j].begin(), un[j].end());
+                }
             }
-        }
-        for (int j = 0; j < np; j++) {
-            std::sort(unc[j].begin(), unc[j].end());
-            printf("spec20_%08x %llu %llu 0x%08llx %zu %llu", rtm::f2u(ps[j]), (unsigned long long)hi, wrong[j],
-                   first[j] == ~0ull ? 0ull : first[j], unc[j].size(), unc_hi[j]);
-            for (size_t k = 0; k < unc[j].size() && k < 256; k++) printf(" 0x%08x", unc[j][k]);
-            printf("\n");
-        }
-        fflush(stdout);
+            for (int j = 0; j < np; j++) {
+                std::sort(unc[j].begin(), unc[j].end());
+                printf("%s%08x %llu %llu 0x%08llx %llu %llu", label, rtm::f2u(pv[j]), (unsigned long long)hi - lo + 1,
+                       wrong[j], first[j] == ~0ull ? 0ull : first[j], unc_n[j], unc_hi[j]);
+                for (size_t k = 0; k < unc[j].size() && k < KEEP; k++) printf(" 0x%08x", unc[j][k]);
+                printf("\n");
+            }
+            fflush(stdout);
+        };
+        sweep("spec20_", 1u, step_hi, false);
+        if (!quick) sweep("spec20above2_", 0x40000001u, 0x7f800000u, true);
     }
     // The exact smallpt domain: r1 = (2*PI) * (m * 2^-23), m < 2^23.
     {

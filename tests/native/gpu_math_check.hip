@@ -248,7 +248,11 @@ extern "C" int gmc_run_spec20(uint32_t lo, uint32_t hi, const float *pspec, int 
     hipLaunchKernelGGL(spec20_kernel, dim3(4096), dim3(256), 0, 0, lo, (uint64_t)hi - lo + 1, ps, np, d);
     // the host's certificate meanwhile
     const int T = 16;
+    // per thread and pspec: the count, and the thread's SPEC20_CAP smallest
+    // (u ascends per thread), so the merged list's first SPEC20_CAP are the
+    // smallest of all however many there are
     std::vector<std::vector<std::vector<uint32_t>>> hl(T, std::vector<std::vector<uint32_t>>(np));
+    std::vector<std::vector<uint64_t>> hn(T, std::vector<uint64_t>(np, 0));
     std::vector<std::thread> th;
     for (int t = 0; t < T; t++)
         th.emplace_back([&, t]() {
@@ -256,7 +260,10 @@ extern "C" int gmc_run_spec20(uint32_t lo, uint32_t hi, const float *pspec, int 
                 for (int j = 0; j < np; j++) {
                     bool amb = false;
                     (void)rt::queue::spec20<false>(rtm::u2f((uint32_t)u), ps.v[j], amb);
-                    if (amb) hl[t][j].push_back((uint32_t)u);
+                    if (amb) {
+                        hn[t][j]++;
+                        if (hl[t][j].size() < (size_t)SPEC20_CAP) hl[t][j].push_back((uint32_t)u);
+                    }
                 }
         });
     for (auto &x : th) x.join();
@@ -275,9 +282,12 @@ extern "C" int gmc_run_spec20(uint32_t lo, uint32_t hi, const float *pspec, int 
         memcpy(wrong_list + (size_t)j * SPEC20_CAP, h[0].wrong_list[j], sizeof(uint32_t) * SPEC20_CAP);
         memcpy(uncert_list + (size_t)j * SPEC20_CAP, h[0].uncert_list[j], sizeof(uint32_t) * SPEC20_CAP);
         std::vector<uint32_t> all;
-        for (int t = 0; t < T; t++) all.insert(all.end(), hl[t][j].begin(), hl[t][j].end());
+        host_uncert[j] = 0;
+        for (int t = 0; t < T; t++) {
+            all.insert(all.end(), hl[t][j].begin(), hl[t][j].end());
+            host_uncert[j] += hn[t][j];
+        }
         std::sort(all.begin(), all.end());
-        host_uncert[j] = all.size();
         for (size_t k = 0; k < (size_t)SPEC20_CAP; k++) host_uncert_list[(size_t)j * SPEC20_CAP + k] = k < all.size() ? all[k] : 0u;
     }
     return 0;

@@ -1,10 +1,14 @@
 """Host check that se-195-project-ray-tracer_amd/csrc/rt_glibc_math.h returns
 the host glibc's bits for powf/expf/sinf/cosf/sincosf over the hot path's
-input domains (exhaustive: ~1e9 inputs per domain, ~40 s on 8 cores), and
+input domains (exhaustive: ~1e9 inputs per domain, about two minutes on 16
+cores), and
 the double pow(x, 20) of the 3.2.03 queue tracer for every float x in (0, 4];
 and that rt_spec20.h's rounding certificate (the queue tracer's specular
 factor without that pow) never certifies a float the host's pow does not give,
-for every float dp in (0, 2] and every pspec of SPEC20_PSPEC."""
+for every float dp in (0, 2] and every pspec of spec20_pspec(); and the same
+three functions above 2, where a non-unit normal takes the kernels: powf(x, 20)
+and pow(x, 20) for every float in (2, +inf], the certificate for every dp
+there and every pspec > 0."""
 import os
 import struct
 import subprocess
@@ -17,13 +21,25 @@ def f32_bits(x):
 
 
 def spec20_pspec():
-    """Every m_spec of the two reference scenes, and 1.0, 1.7, 0.0123 (float32
-    bit patterns, ascending)."""
+    """Every m_spec of the two reference scenes, and 1.0, 1.7, 0.0123, +inf,
+    3e38 and 1e-42 (float32 bit patterns, ascending; the device sweep takes at
+    most 16)."""
     import oracle_lib as O
     W, nw = O.whitted_scene()
     Q, nq = O.queue_scene()
     vals = [W[i].m_Spec for i in range(nw)] + [Q[i].m_spec for i in range(nq)] + [1.0, 1.7, 0.0123]
-    return sorted({f32_bits(v) for v in vals})
+    vals += [float("inf"), 3e38, 1e-42]
+    bits = sorted({f32_bits(v) for v in vals})
+    assert len(bits) <= 16
+    return bits
+
+
+def spec20_pspec_positive():
+    """spec20_pspec() without 0: the kernel evaluates the factor only where
+    m_spec > 0 (queue.hip shade_hit), and above dp = 2^51.2, where x^20
+    overflows a double, 0 * inf is a NaN that is never certified -- 6.4e8
+    inputs that say nothing about the certificate."""
+    return [b for b in spec20_pspec() if 0 < b < 0x80000000]
 
 
 # The share of uncertified inputs among the dp bit patterns [0x3c000000,
@@ -31,6 +47,9 @@ def spec20_pspec():
 # leave to the exact path: 2^-20, so that "certify nothing" cannot pass.
 SPEC20_RANGE = 0x40000000 - 0x3c000000 + 1
 SPEC20_MAX_UNCERTIFIED = SPEC20_RANGE >> 20
+# The second range, dp in (2, +inf], and its cap: 2^-20 of its bit patterns.
+SPEC20_ABOVE2 = (0x40000001, 0x7f800000)
+SPEC20_ABOVE2_MAX_UNCERTIFIED = (SPEC20_ABOVE2[1] - SPEC20_ABOVE2[0] + 1) >> 20
 
 
 def test_glibc_math_exhaustive():
@@ -40,16 +59,23 @@ def test_glibc_math_exhaustive():
     out = subprocess.run([os.path.join(HERE, "glibc_math_check")] + ["0x%08x" % b for b in pspec], check=True,
                          capture_output=True, text=True).stdout
     rows = [l.split() for l in out.strip().splitlines()]
-    assert len(rows) == 17 + len(pspec), out
+    pos = spec20_pspec_positive()
+    assert len(rows) == 19 + len(pspec) + len(pos), out
     bad = [r for r in rows if int(r[2]) != 0]
     assert not bad, bad
-    assert sum(int(r[1]) for r in rows if not r[0].startswith("spec20_")) > 12e9
-    spec = {int(r[0][7:], 16): r for r in rows if r[0].startswith("spec20_")}
-    assert sorted(spec) == pspec
-    for b, r in spec.items():
-        uncertified, in_range = int(r[4]), int(r[5])
-        print("spec20 pspec 0x%08x: %s inputs, certified-but-wrong %s, uncertified %d (%d at or above 0x3c000000): %s"
-              % (b, r[1], r[2], uncertified, in_range, " ".join(r[6:])))
-        assert int(r[1]) == 0x40000000 and len(r) == 6 + uncertified
-        assert in_range <= SPEC20_MAX_UNCERTIFIED, (hex(b), in_range)
-    assert any(int(r[4]) > 0 for r in spec.values()), "no pspec has an uncertified input: nothing reaches the exact path"
+    assert sum(int(r[1]) for r in rows if not r[0].startswith("spec20")) > 14e9
+    assert {"powf_y20_above2", "pow_d_y20_above2"} <= {r[0] for r in rows}
+    for prefix, want, checked, cap in (("spec20_", pspec, 0x40000000, SPEC20_MAX_UNCERTIFIED),
+                                       ("spec20above2_", pos, SPEC20_ABOVE2[1] - SPEC20_ABOVE2[0] + 1,
+                                        SPEC20_ABOVE2_MAX_UNCERTIFIED)):
+        spec = {int(r[0][len(prefix):], 16): r for r in rows if r[0].startswith(prefix)}
+        assert sorted(spec) == want
+        for b, r in sorted(spec.items()):
+            uncertified, in_range = int(r[4]), int(r[5])
+            print("%s pspec 0x%08x: %s inputs, certified-but-wrong %s, uncertified %d (%d at or above 0x3c000000): %s"
+                  % (prefix, b, r[1], r[2], uncertified, in_range, " ".join(r[6:14])))
+            # the program lists the 256 smallest uncertified inputs: all of them up to that count
+            assert int(r[1]) == checked and len(r) == 6 + min(uncertified, 256)
+            assert in_range <= cap, (hex(b), in_range)
+        assert any(int(r[4]) > 0 for r in spec.values()), \
+            "no pspec has an uncertified input: nothing reaches the exact path"
