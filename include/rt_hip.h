@@ -134,6 +134,50 @@ int rtw_render_ocl(const rt_primitive *prims, int nprims, uint32_t *xrgb, int w,
 int rtw_render_ocl_async(const rt_primitive *d_prims, int nprims, uint32_t *d_xrgb, int w, int h,
                          uint64_t *d_counters, void *stream);
 
+/* What colour does the tracer compute along this ray?  For each of the caller's
+ * rays (d_rays: device memory, 6 floats per ray, o.xyz d.xyz, used as given:
+ * the direction is NOT normalised) one sub-sample of Engine_Render
+ * (raytracer.cpp:353-511) with o_Ray = refl_Ray = refr_Ray = that ray,
+ * input_Rindex = 1 and the node arrays reset: the root Engine_Raytrace call,
+ * the 62 children in breadth-first order (each traced iff its parent's refl /
+ * refr > 0; a total-internal-reflection node's refraction child with the
+ * refr_Ray variable as the earlier calls left it -- the last node before it
+ * that wrote one, else the caller's own ray) and the back-accumulation.
+ *   d_color[3r .. 3r+2]  tr_Color_{x,y,z}[0] after the back-accumulation.  The
+ *                        reference adds both children's shares to it, traced
+ *                        or not, so a channel is never -0.0;
+ *   d_t[r]               tr_dist[0]: the root's distance, 1e6f on a miss
+ *                        (nullable);
+ *   d_id[r]              the root call's return: the primitive index or -1
+ *                        (nullable).
+ * The sub-sample grid, the x28 / x64 scale and the pack stay with the caller
+ * (rtamd.scenes.whitted_camera_rays / whitted_pack restate the frame's).
+ * flags: RTW_TRACE_OCL selects openCLcode.h / openCLcode.cl's semantics (a
+ * light hit adds the light's colour, a shadow ray's occluders are the
+ * primitives with m_Light < 1, the reflection child is folded first).
+ * d_counters (nullable, device u64[4], accumulated into): rtw_render's four.
+ * Every float is the reference's, bit for bit, for any ray and any primitive
+ * floats; where the reference's value is a NaN, some NaN.
+ *
+ * Ordered on `stream` as rtw_render_async is -- serialised with the other
+ * level-pass frames on the device, whose arena it shares -- but on that one
+ * stream only.  The rays run in slabs of up to 18 M, one after the other
+ * (RT_WHITTED_TRACE_SLAB=<rays>, rounded up to 64, forces small ones and
+ * RT_WHITTED_QUEUE_CAP a small record pool: test hooks, the same bits).  NOT
+ * promised to be graph-capturable: the arena may grow, and sizing the record
+ * pool reads a host flag.  nrays == 0 is RT_OK and launches nothing.  The
+ * outputs must not alias the inputs; an output that is not asked for is not
+ * written.  RT_ERR_INVALID before any device work: a null d_prims, d_rays or
+ * d_color; nprims outside 1..64; unknown flag bits; nrays above INT32_MAX. */
+#define RTW_TRACE_OCL 0x1
+int rtw_trace_async(const rt_primitive *d_prims, int nprims, const float *d_rays, size_t nrays, int flags,
+                    float *d_color, float *d_t, int *d_id, uint64_t *d_counters, void *stream);
+/* Blocking, host buffers; counters (nullable, host u64[4]) receives this
+ * call's counts.  The device copies are the call's own allocation, freed
+ * before it returns. */
+int rtw_trace(const rt_primitive *prims, int nprims, const float *rays, size_t nrays, int flags,
+              float *color, float *t, int *id, uint64_t *counters);
+
 /* ------------------------------------------------------------ smallpt */
 #define SPT_PATH_TRACING 0       /* RadiancePathTracing    geomfunc.h:167-338 */
 #define SPT_DIRECT_LIGHTING 1    /* RadianceDirectLighting geomfunc.h:340-483 */

@@ -116,7 +116,7 @@ int state(DeviceState **out)
             delete st;
             return fail_hip(e, "hipEventCreate");
         }
-        e = hipHostMalloc((void **)&st->pool_ovf, POOL_FITS * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
+        e = hipHostMalloc((void **)&st->pool_ovf, (POOL_FITS + POOL_TRACE_BUCKETS) * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
         if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&st->pool_ovf_dev, st->pool_ovf, 0);
         if (e != hipSuccess) {
             (void)hipEventDestroy(st->wf_done);
@@ -125,7 +125,7 @@ int state(DeviceState **out)
             delete st;
             return fail_hip(e, "hipHostMalloc");
         }
-        memset(st->pool_ovf, 0, POOL_FITS * sizeof(int));
+        memset(st->pool_ovf, 0, (POOL_FITS + POOL_TRACE_BUCKETS) * sizeof(int));
         g_states[dev] = st;
         // The second stream (two-slab level-pass frames) is created with the
         // state, not at its first use: created mid-run it ran the 1080p
@@ -165,8 +165,32 @@ int scratch(DeviceState &st, int slot, size_t bytes, void **out)
     return RT_OK;
 }
 
+// RT_POOL_FRAC (test hook: a small first pool, which overflows) over `initial`.
+static double first_fraction(double initial)
+{
+    if (const char *e = getenv("RT_POOL_FRAC")) {
+        const double v = atof(e);
+        if (v > 0.0 && v < POOL_FRAC_MAX) return v;
+    }
+    return initial;
+}
+
 double pool_fraction(DeviceState &st, int which, long long trees, double initial, int **flag_dev)
 {
+    if (which == POOL_WHITTED_TRACE) {
+        int b = 0;
+        while (b < POOL_TRACE_BUCKETS - 1 && (1LL << b) < trees) b++;
+        volatile int *flag = st.pool_ovf + POOL_FITS + b;
+        if (st.trace_frac[b] == 0.0) {
+            st.trace_frac[b] = first_fraction(initial);
+        } else if (*flag) {
+            const double f = st.trace_frac[b] * 1.25;
+            st.trace_frac[b] = f < POOL_FRAC_MAX ? f : POOL_FRAC_MAX;
+        }
+        *flag = 0;
+        *flag_dev = st.pool_ovf_dev + POOL_FITS + b;
+        return st.trace_frac[b];
+    }
     int i = 0;
     while (i < POOL_FITS && !(st.pool_fit[i].which == which && st.pool_fit[i].trees == trees)) i++;
     volatile int *flag;
@@ -182,11 +206,7 @@ double pool_fraction(DeviceState &st, int which, long long trees, double initial
         st.pool_fit_next = (i + 1) % POOL_FITS;
         st.pool_fit[i].which = which;
         st.pool_fit[i].trees = trees;
-        st.pool_fit[i].frac = initial;
-        if (const char *e = getenv("RT_POOL_FRAC")) {      // test hook: a small first pool (it overflows)
-            const double v = atof(e);
-            if (v > 0.0 && v < POOL_FRAC_MAX) st.pool_fit[i].frac = v;
-        }
+        st.pool_fit[i].frac = first_fraction(initial);
         flag = st.pool_ovf + i;
         *flag = 0;
     } else {

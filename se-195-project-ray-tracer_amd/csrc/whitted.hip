@@ -25,7 +25,9 @@
 //   * m_SX / m_SY are sequential float sums in the reference (:309,:524,:526):
 //     the host tabulates them once per frame size (exact same float adds);
 //   * glibc powf/expf are reproduced by rt_glibc_math.h (double-precision,
-//     op-for-op restatement of glibc 2.35's FMA build).
+//     op-for-op restatement of glibc 2.35's FMA build);
+//   * rtw_trace_async runs the same level pass on rays the caller supplies
+//     (one tree per ray: "The caller's rays as trees" below).
 #include "rt_common.h"
 #include "rt_glibc_math.h"
 #include "rt_levelq.h"
@@ -234,6 +236,30 @@ __device__ __forceinline__ ray3 primary(int sub, float SX, float SY, float DX, f
     return r;
 }
 
+// Where a tree's root ray comes from (tir_kernel's and fixup_kernel's View):
+// the frame's camera -- tree = sub * npix + pixel, the ray rebuilt from the
+// m_SX / m_SY tables -- or the caller's ray array (rtw_trace_async: tree = the
+// ray's index within the slab, six floats used as given).
+struct WfArgs;
+__device__ __forceinline__ int slab_row(const WfArgs &A, int r);
+struct CameraView {
+    const float *__restrict__ sx_tab;
+    const float *__restrict__ sy_tab;
+    float DX, DY;
+    __device__ __forceinline__ ray3 root(const WfArgs &A, int tree) const;
+};
+struct RayView {
+    const float *__restrict__ rays;      // the slab's first ray
+    __device__ __forceinline__ ray3 root(const WfArgs &, int tree) const
+    {
+        const float *p = rays + 6 * (size_t)tree;
+        ray3 r;
+        r.o = mk(p[0], p[1], p[2]);
+        r.d = mk(p[3], p[4], p[5]);
+        return r;
+    }
+};
+
 // Builds the SoA scene image from the reference's 96-byte AoS primitives:
 // one wave, a lane per primitive (prims::fill_lists).  The shadow loop's
 // occluders are the primitives with m_Light == 0 (raytracer.cpp:100) or,
@@ -337,6 +363,7 @@ struct WfArgs {
     int *rinfo;               // [ntrees] hit primitive | INFO_*
     float4 *psum;             // [npix] sum (xyz) of the colours of the pixel's leading childless trees,
                               //   in sub-sample order, and (w, int bits) the first sub-sample not in it
+                              //   (frames only: a trace call's arena has none)
     int2 *rchild;             // [ntrees] pool slots (level 1) of refl / refr child, -1 if none
     unsigned *fixbits;        // [ntrees/32 + 1] tree flagged for fixup
     int *fixlist;             // [fixcap] flagged trees (fixup scans fixbits when more)
@@ -367,6 +394,13 @@ __device__ __forceinline__ int slab_row(const WfArgs &A, int r)
     const int g = r >> 4;
     const int pg = A.row_count == 1 ? g * A.row_stride : (g / A.row_count) * A.row_stride + g % A.row_count;
     return A.row_begin + (pg << 4) + (r & 15);
+}
+
+__device__ __forceinline__ ray3 CameraView::root(const WfArgs &A, int tree) const
+{
+    const int sub = tree / A.npix, pix = tree % A.npix;
+    const int x = pix % A.w, y = slab_row(A, pix / A.w);
+    return primary(sub, sx_tab[x], sy_tab[y], DX, DY, A.side);
 }
 
 // Per-segment item limit of a level based at `base` (the pages left in the pool).
@@ -599,9 +633,9 @@ __device__ bool find_node(const WfArgs &A, int tree, int j, int &lvl, int &slot)
 // ray of the last node before this one in BFS order that wrote one, or the
 // primary ray (raytracer.cpp:231-233, :373-374, :412).  Every node before it
 // has been traced by now (levels <= L); queue that child into level L+1.
+template <class View>
 __global__ void __launch_bounds__(64)
-tir_kernel(WfArgs A, int L, const float *__restrict__ sx_tab, const float *__restrict__ sy_tab, float DX,
-           float DY)
+tir_kernel(WfArgs A, int L, View view)
 {
     const int nt = min(counter(A, C_TIR + L), A.tcap);
     const int nbase = level_base(A, L + 1);
@@ -631,11 +665,7 @@ tir_kernel(WfArgs A, int L, const float *__restrict__ sx_tab, const float *__res
             found = true;
         }
         if (broken) { flag_tree(A, tree); continue; }
-        if (!found) {
-            const int sub = tree / A.npix, pix = tree % A.npix;
-            const int x = pix % A.w, y = slab_row(A, pix / A.w);
-            r = primary(sub, sx_tab[x], sy_tab[y], DX, DY, A.side);
-        }
+        if (!found) r = view.root(A, tree);
         const int seg = tree & (NSEG - 1);
         const int k = atomicAdd(&counter(A, C_SEG + (L + 1) * NSEG + seg), 1);
         if (k >= lim) { flag_tree(A, tree); continue; }
@@ -806,10 +836,9 @@ __device__ __forceinline__ int level_of(int i) { return 31 - __builtin_clz(i + 1
 // carried across nodes (cur_refr), back-accumulation in decreasing index.
 // Writes the tree's final level-0 colour into rcol[tree]; counts only the
 // nodes the level pass did not trace.
-template <bool COUNT>
+template <bool COUNT, class View>
 __global__ void __launch_bounds__(64)
-fixup_kernel(WfArgs A, const float *__restrict__ sx_tab, const float *__restrict__ sy_tab, float DX, float DY,
-             unsigned long long *__restrict__ counters)
+fixup_kernel(WfArgs A, View view, unsigned long long *__restrict__ counters)
 {
     const int nfix = counter(A, C_FIX);
     if (nfix == 0) return;
@@ -838,11 +867,9 @@ fixup_kernel(WfArgs A, const float *__restrict__ sx_tab, const float *__restrict
         const int bit = __builtin_ctz(bits);
         bits &= bits - 1u;
         const int tree = scan ? (f << 5) + bit : A.fixlist[f];
-        const int sub = tree / A.npix, pix = tree % A.npix;
-        const int x = pix % A.w, y = slab_row(A, pix / A.w);
         NodeStore ns;
         unsigned long long todo = 1, traced = 0;
-        const ray3 root = primary(sub, sx_tab[x], sy_tab[y], DX, DY, A.side);
+        const ray3 root = view.root(A, tree);
         ray3 cur_refr = root;          // the caller's refr_Ray variable (:373-374)
         while (todo) {
             const int i = __builtin_ctzll(todo);
@@ -928,6 +955,103 @@ fixup_kernel(WfArgs A, const float *__restrict__ sx_tab, const float *__restrict
     }
 }
 
+// ---------------------------------------------------------------------------
+// The caller's rays as trees (rtw_trace_async): tree = the ray's index within
+// the slab, nsub = 1.  These two kernels replace root_kernel and final_kernel;
+// the levels between run as for a frame, tir_kernel and fixup_kernel reading a
+// tree's root ray from the ray array (RayView).
+
+// Level 0: a lane per ray.  The block's 256 x 6 floats come in as six
+// coalesced dword loads per lane and are read back ray-wise from LDS
+// (load_scene's barrier publishes them).  Those reads are at a stride of 6
+// floats, two lanes to a bank; padding a ray to 7 floats removes that and
+// changed nothing (kernel 781.0 against 780.7 us for 17.1 M rays, calls within
+// 0.7 % either way: profiles/r25/INDEX.md), so the plain layout stays.  A lane past the slab's rays runs an
+// all-NaN ray through the nearest-hit loop (as in prims_query.hip: it takes
+// nothing and asks for no exact-sqrt redo) and neither shades, queues, records
+// nor counts.  Every ray's root record is written: the final kernel reads all.
+template <bool COUNT>
+__global__ void __launch_bounds__(256, RT_WH_MINWAVES)
+trace_root_kernel(WfArgs A, const float *__restrict__ rays, unsigned long long *__restrict__ counters)
+{
+    __shared__ Scene S;
+    __shared__ float stage[256 * 6];
+    const int first = blockIdx.x * 256;                       // (< ntrees: the grid is ceil(ntrees / 256))
+    const int nfl = 6 * min(256, A.ntrees - first);
+    const float *__restrict__ src = rays + 6 * (size_t)first;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        const int i = k * 256 + (int)threadIdx.x;
+        if (i < nfl) stage[i] = src[i];
+    }
+    load_scene(S, A.scene);
+    const int tree = first + (int)threadIdx.x;
+    const bool active = tree < A.ntrees;
+    const float nan = __builtin_nanf("");
+    ray3 rp[1];
+    rp[0].o = mk(nan, nan, nan);
+    rp[0].d = mk(nan, nan, nan);
+    if (active) {
+        const float *p = stage + 6 * threadIdx.x;
+        rp[0].o = mk(p[0], p[1], p[2]);
+        rp[0].d = mk(p[3], p[4], p[5]);
+    }
+    float nd[1];
+    int np_[1], nr[1];
+    prims::nearest_n<1, NearestTraits>(S, rp, nd, np_, nr);
+    Counts cnt = {0, 0, 0, 0};
+    Hit hh;
+    bool tir = false;
+    if (active) {
+        hh = shade_hit<COUNT>(S, rp[0], 1.0f, nd[0], np_[0], nr[0], cnt, A.ocl);
+        tir = hh.refr > 0 && !hh.refr_ray_ok;
+        if (tir) cnt.tir++;
+    }
+    const int wave_id = (blockIdx.x << 2) + (threadIdx.x >> 6);
+    const int2 ch = queue_children(A, 0, 0, wave_id, active, tree, tree, 0, hh, tir);
+    if (active) {
+        A.rcol[tree] = make_float4(hh.acc.x, hh.acc.y, hh.acc.z, hh.dist);
+        A.rinfo[tree] = node_info(hh, tir);
+        A.rchild[tree] = ch;
+    }
+    if (COUNT) {
+        const unsigned long long c[4] = {cnt.traced, cnt.shadow, cnt.tests, cnt.tir};
+        flush_counters<4>(counters, c);
+    }
+}
+
+// Level 0 folded with level 1 (final after backacc_kernel), or the root as
+// fixup_kernel left it, and the ray's outputs.  The reference adds both
+// children's shares to tr_Color[0] whether it traced them or not (0 for an
+// untraced one, raytracer.cpp:476-511), so a root colour of -0.0 (a light
+// colour's channel under the OpenCL semantics, which shade_hit assigns where
+// openCLcode.h:180-182 adds it to 0) comes out as +0.0: `+ 0.0f` is that add
+// -- the identity on every other value, and a node that is not a light never
+// holds -0.0 (its colour is 0 + terms).
+__global__ void __launch_bounds__(256)
+trace_final_kernel(WfArgs A, float *__restrict__ color, float *__restrict__ t, int *__restrict__ id)
+{
+    __shared__ Scene S;
+    load_scene(S, A.scene);
+    const int tree = blockIdx.x * 256 + (int)threadIdx.x;
+    if (tree >= A.ntrees) return;
+    float4 c = A.rcol[tree];
+    const int info = A.rinfo[tree];
+    const int2 ch = A.rchild[tree];
+    if (!flagged(A, tree) && (ch.x >= 0 || ch.y >= 0)) {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 cx = ch.x >= 0 ? folded<0>(A, S, ch.x) : z;
+        const float4 cy = ch.y >= 0 ? folded<0>(A, S, ch.y) : z;
+        c = accumulate(S, c, info, ch, cx, cy, A.ocl);
+    }
+    float *o = color + 3 * (size_t)tree;
+    o[0] = c.x + 0.0f;
+    o[1] = c.y + 0.0f;
+    o[2] = c.z + 0.0f;
+    if (t) t[tree] = c.w;
+    if (id) id[tree] = (info & 0xff) < MAXP ? (info & 0xff) : -1;
+}
+
 }  // namespace whitted
 }  // namespace rt
 
@@ -1001,7 +1125,12 @@ int view_tables(rtrt::DeviceState &st, hipStream_t s, int w, int h, bool ocl, fl
 // Device arena of the level pass (scratch slot SLOT_WF, grow-only) for a slab
 // of `rows` rows: per tree a root record and a fixup bit; the record pool of
 // levels 1..5; per level 0..4 a TIR list.
-int wavefront_arena(rtrt::DeviceState &st, int slot, int w, int rows, int nsub, rt::whitted::WfArgs *A)
+// A trace call's arena (rtw_trace_async: w rays, one row, nsub = 1) has no
+// per-pixel sums and learns its pool fraction under its own key, so a trace
+// never moves a frame size's fraction: with the same fraction it is the arena
+// of a frame of as many trees less that frame's psum.
+int wavefront_arena(rtrt::DeviceState &st, int slot, int w, int rows, int nsub, rt::whitted::WfArgs *A,
+                    int pool_key = rtrt::POOL_WHITTED, bool with_psum = true)
 {
     using namespace rt::whitted;
     const size_t T = (size_t)w * rows * nsub;
@@ -1009,7 +1138,7 @@ int wavefront_arena(rtrt::DeviceState &st, int slot, int w, int rows, int nsub, 
     // RT_WHITTED_QUEUE_CAP lowers the pool (test hook: exercises the
     // overflow -> fixup path).
     int *ovf = nullptr;
-    size_t P = (size_t)(T * rtrt::pool_fraction(st, rtrt::POOL_WHITTED, (long long)T, POOL_FRAC, &ovf));
+    size_t P = (size_t)(T * rtrt::pool_fraction(st, pool_key, (long long)T, POOL_FRAC, &ovf));
     if (const char *e = getenv("RT_WHITTED_QUEUE_CAP")) {
         const long long v = atoll(e);
         if (v > 0 && (size_t)v < P) P = (size_t)v;
@@ -1022,7 +1151,7 @@ int wavefront_arena(rtrt::DeviceState &st, int slot, int w, int rows, int nsub, 
         a.take(A->scene, sizeof(Scene));
         a.take(A->rcol, T * 16);
         a.take(A->rinfo, T * 4);
-        a.take(A->psum, (size_t)w * rows * 16);
+        a.take(A->psum, with_psum ? (size_t)w * rows * 16 : 0);
         a.take(A->rchild, T * 8);
         a.take(A->fixbits, FB);
         a.take(A->fixlist, FC * 4);
@@ -1054,12 +1183,13 @@ int launch_wavefront(const rt::whitted::WfArgs &A, int w, int rows, int row_end,
     static const int level_blocks = rtrt::resident_blocks(level_kernel<COUNT>);
     const dim3 tiles((w + 15) / 16, (rows + 15) / 16), block(256);
     const int qblocks = (int)std::min<long long>(((long long)A.pool + 255) / 256, 2048);
+    const CameraView view{d_sx, d_sy, DX, DY};
     hipLaunchKernelGGL(root_kernel<COUNT>, tiles, block, 0, s, A, row_end, d_sx, d_sy, DX, DY, cnt);
     for (int L = 1; L < LEVELS; L++) {
-        hipLaunchKernelGGL(tir_kernel, dim3(64), dim3(64), 0, s, A, L - 1, d_sx, d_sy, DX, DY);   // (256 / 1024 blocks: level)
+        hipLaunchKernelGGL(tir_kernel<CameraView>, dim3(64), dim3(64), 0, s, A, L - 1, view);   // (256 / 1024 blocks: level)
         hipLaunchKernelGGL(level_kernel<COUNT>, dim3(level_blocks), block, 0, s, A, L, cnt);
     }
-    hipLaunchKernelGGL(fixup_kernel<COUNT>, dim3(256), dim3(64), 0, s, A, d_sx, d_sy, DX, DY, cnt);
+    hipLaunchKernelGGL((fixup_kernel<COUNT, CameraView>), dim3(256), dim3(64), 0, s, A, view, cnt);
     // Back-accumulation: levels (3 <- 4 <- 5), then (1 <- 2 <- 3); the final
     // kernel folds 0 <- 1.
     static_assert(LEVELS == 6, "the back-accumulation schedule assumes levels 0..5");
@@ -1164,7 +1294,154 @@ int render_async(const rt_primitive *d_prims, int nprims, uint32_t *d_xrgb, int 
     return frame.end();
 }
 
+template <bool COUNT>
+int launch_trace(const rt::whitted::WfArgs &A, const float *d_rays, float *d_color, float *d_t, int *d_id,
+                 unsigned long long *cnt, hipStream_t s)
+{
+    using namespace rt::whitted;
+    static const int level_blocks = rtrt::resident_blocks(level_kernel<COUNT>);
+    const dim3 grid((A.ntrees + 255) / 256), block(256);
+    // (a small batch: no more level blocks than its pool has pages for)
+    const int qblocks = (int)std::min<long long>(((long long)A.pool + 255) / 256, 2048);
+    const int lblocks = (int)std::min<long long>(level_blocks, ((long long)A.pool + 255) / 256);
+    const RayView view{d_rays};
+    hipLaunchKernelGGL(trace_root_kernel<COUNT>, grid, block, 0, s, A, d_rays, cnt);
+    for (int L = 1; L < LEVELS; L++) {
+        hipLaunchKernelGGL(tir_kernel<RayView>, dim3(64), dim3(64), 0, s, A, L - 1, view);
+        hipLaunchKernelGGL(level_kernel<COUNT>, dim3(lblocks), block, 0, s, A, L, cnt);
+    }
+    hipLaunchKernelGGL((fixup_kernel<COUNT, RayView>), dim3(256), dim3(64), 0, s, A, view, cnt);
+    static_assert(LEVELS == 6, "the back-accumulation schedule assumes levels 0..5");
+    hipLaunchKernelGGL(backacc_kernel<2>, dim3(qblocks), block, 0, s, A, 3);
+    hipLaunchKernelGGL(backacc_kernel<2>, dim3(qblocks), block, 0, s, A, 1);
+    hipLaunchKernelGGL(trace_final_kernel, grid, block, 0, s, A, d_color, d_t, d_id);
+    return rtrt::check_launch("rtw trace kernels");
+}
+
+// Rays per slab of a trace call: as many trees as a frame's slab holds, within
+// the queued items' tree word.  RT_WHITTED_TRACE_SLAB=<rays> (test hook,
+// rounded up to 64) forces small slabs.
+long long trace_slab_rays()
+{
+    long long slab = std::min<long long>(SLAB_TREES, (long long)rt::whitted::TREE_MASK + 1);
+    if (const char *e = getenv("RT_WHITTED_TRACE_SLAB")) {
+        const long long v = atoll(e);
+        if (v > 0) slab = std::min(slab, (v + 63) / 64 * 64);
+    }
+    return slab;
+}
+
+// The colour the tracer computes along each of the caller's rays: the rays as
+// trees of the level pass (tree = ray index within the slab, nsub = 1), slab
+// after slab on the caller's stream, under the frame bracket (the arena is
+// the frames').
+int trace_async(const rt_primitive *d_prims, int nprims, const float *d_rays, size_t nrays, bool ocl, float *d_color,
+                float *d_t, int *d_id, uint64_t *d_counters, void *stream)
+{
+    rtrt::DeviceState *st;
+    int rc = rtrt::state(&st);
+    if (rc) return rc;
+    std::lock_guard<std::recursive_mutex> lk(st->mu);
+    hipStream_t s = (hipStream_t)stream;
+    rtrt::Frame frame(*st, s, "rtw_trace_async");
+    if ((rc = frame.begin())) return rc;
+    const long long slab = trace_slab_rays();
+    rt::whitted::WfArgs A;
+    if ((rc = wavefront_arena(*st, SLOT_WF, (int)std::min<long long>((long long)nrays, slab), 1, 1, &A,
+                              rtrt::POOL_WHITTED_TRACE, false)))
+        return rc;
+    A.side = 1;
+    A.nsub = 1;
+    A.ocl = ocl;
+    A.row_begin = 0;
+    A.row_stride = 1;
+    A.row_count = 1;
+    unsigned long long *cnt = (unsigned long long *)d_counters;
+    for (long long first = 0; first < (long long)nrays; first += slab) {
+        const int n = (int)std::min<long long>(slab, (long long)nrays - first);
+        A.w = A.npix = A.ntrees = n;
+        const int nz0 = rtrt::words16(sizeof(int) * rt::whitted::C_TOTAL * rt::whitted::CSTRIDE);
+        const int nz1 = rtrt::words16(sizeof(unsigned) * (((size_t)n + 31) / 32));
+        const int pblocks = std::min(1024, std::max(1, (nz0 + nz1 + 255) / 256));
+        hipLaunchKernelGGL(rt::whitted::prep_kernel, dim3(pblocks), dim3(256), 0, s, first == 0 ? d_prims : nullptr,
+                           nprims, (rt::whitted::Scene *)A.scene, (uint4 *)A.count, nz0, (uint4 *)A.fixbits, nz1, ocl);
+        const float *r = d_rays + 6 * (size_t)first;
+        float *c = d_color + 3 * (size_t)first, *t = d_t ? d_t + first : nullptr;
+        int *id = d_id ? d_id + first : nullptr;
+        rc = cnt ? launch_trace<true>(A, r, c, t, id, cnt, s) : launch_trace<false>(A, r, c, t, id, cnt, s);
+        if (rc) return rc;
+    }
+    return frame.end();
+}
+
+// What rtw_trace_async and rtw_trace refuse before any device work.
+int trace_args(const char *who, const void *prims, int nprims, const void *rays, size_t nrays, int flags,
+               const void *color)
+{
+    char msg[160];
+    const char *why = nullptr;
+    if (!prims || !rays || !color) why = "null primitives, rays or colour output";
+    else if (nprims < 1 || nprims > rt::whitted::MAXP) why = "nprims outside 1..64";
+    else if (flags & ~RTW_TRACE_OCL) why = "unknown flag bits";
+    else if (nrays > (size_t)INT32_MAX) why = "too many rays";
+    if (!why) return RT_OK;
+    snprintf(msg, sizeof(msg), "%s: %s", who, why);
+    return rtrt::fail(RT_ERR_INVALID, msg);
+}
+
 }  // namespace
+
+extern "C" int rtw_trace_async(const rt_primitive *d_prims, int nprims, const float *d_rays, size_t nrays, int flags,
+                               float *d_color, float *d_t, int *d_id, uint64_t *d_counters, void *stream)
+{
+    int rc = trace_args("rtw_trace_async", d_prims, nprims, d_rays, nrays, flags, d_color);
+    if (rc || nrays == 0) return rc;
+    return trace_async(d_prims, nprims, d_rays, nrays, (flags & RTW_TRACE_OCL) != 0, d_color, d_t, d_id, d_counters,
+                       stream);
+}
+
+// Blocking, host buffers.  The device copies live in one allocation of the
+// call's own, freed before it returns: the cached staging slots stay what the
+// frames made them, so a trace caches no more than its arena.
+extern "C" int rtw_trace(const rt_primitive *prims, int nprims, const float *rays, size_t nrays, int flags,
+                         float *color, float *t, int *id, uint64_t *counters)
+{
+    int rc = trace_args("rtw_trace", prims, nprims, rays, nrays, flags, color);
+    if (rc) return rc;
+    if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0;
+    if (nrays == 0) return RT_OK;
+    rtrt::DeviceState *st;
+    if ((rc = rtrt::state(&st))) return rc;
+    std::lock_guard<std::recursive_mutex> lk(st->mu);
+    const auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_rays = r256(sizeof(rt_primitive) * (size_t)nprims), o_col = o_rays + r256(24 * nrays),
+                 o_t = o_col + r256(12 * nrays), o_id = o_t + r256(4 * nrays), o_cnt = o_id + r256(4 * nrays),
+                 total = o_cnt + 256;
+    char *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, total);
+    if (e != hipSuccess) return rtrt::fail_hip(e, "rtw_trace hipMalloc");
+    hipStream_t s = st->stream;
+    e = hipMemcpyAsync(d, prims, sizeof(rt_primitive) * (size_t)nprims, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_rays, rays, 24 * nrays, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && counters) e = hipMemsetAsync(d + o_cnt, 0, 4 * sizeof(uint64_t), s);
+    if (e != hipSuccess) rc = rtrt::fail_hip(e, "rtw_trace H2D");
+    if (!rc)
+        rc = trace_async((const rt_primitive *)d, nprims, (const float *)(d + o_rays), nrays,
+                         (flags & RTW_TRACE_OCL) != 0, (float *)(d + o_col), t ? (float *)(d + o_t) : nullptr,
+                         id ? (int *)(d + o_id) : nullptr, counters ? (uint64_t *)(d + o_cnt) : nullptr, s);
+    if (!rc) {
+        e = hipMemcpyAsync(color, d + o_col, 12 * nrays, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && t) e = hipMemcpyAsync(t, d + o_t, 4 * nrays, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && id) e = hipMemcpyAsync(id, d + o_id, 4 * nrays, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && counters)
+            e = hipMemcpyAsync(counters, d + o_cnt, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) rc = rtrt::fail_hip(e, "rtw_trace D2H");
+    }
+    e = hipStreamSynchronize(s);          // (also before the free: the kernels read d)
+    if (e != hipSuccess && !rc) rc = rtrt::fail_hip(e, "rtw_trace sync");
+    (void)hipFree(d);
+    return rc;
+}
 
 extern "C" int rtw_render_async(const rt_primitive *d_prims, int nprims, uint32_t *d_xrgb, int w,
                                 int h, int row_begin, int row_end, uint64_t *d_counters,

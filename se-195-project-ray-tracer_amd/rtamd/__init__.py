@@ -18,7 +18,9 @@ what the tests, bench.py and __graft_entry__ drive.
     Queries  : SmallptScene.query() / .radiance() on a prepared smallpt scene;
                PrimScene.query() on the Whitted or the queue tracer's
                primitives (rtp_query_async): nearest hit, shadowed or not,
-               the first occluder
+               the first occluder;
+               whitted_trace() / whitted_trace_async(): the colour the Whitted
+               tracer computes along the caller's rays (rtw_trace_async)
 """
 import ctypes as C
 
@@ -29,10 +31,11 @@ from .device import SmallptDeviceFrame
 from ._lib import (Camera, Float4, Primitive, QPrimitive, RTError, Sphere, Vec3, check, device_count, entry, lib,
                    set_device, SPT_COST_MAX, SPT_COUNT_RAYS, SPT_LIST_SET, SPT_DIRECT_LIGHTING, SPT_PATH_TRACING,
                    SPT_QUERY_ANY, SPT_QUERY_NEAREST, SPT_QUERY_OCCLUDER, RTP_QUERY_NEAREST, RTP_QUERY_SHADOW,
-                   RTP_QUERY_OCCLUDER)
+                   RTP_QUERY_OCCLUDER, RTW_TRACE_OCL)
 
 __all__ = ["Camera", "Primitive", "QPrimitive", "Float4", "Sphere", "Vec3", "RTError", "scenes", "lib", "check",
-           "device_count", "set_device", "whitted_render", "queue_render", "SmallptFrame", "SmallptScene",
+           "device_count", "set_device", "whitted_render", "whitted_trace", "whitted_trace_async",
+           "RTW_TRACE_OCL", "queue_render", "SmallptFrame", "SmallptScene",
            "SmallptMulti", "SmallptDeviceFrame", "PrimScene",
            "SPT_PATH_TRACING", "SPT_DIRECT_LIGHTING", "SPT_COUNT_RAYS", "SPT_COST_MAX", "SPT_LIST_SET",
            "SPT_QUERY_NEAREST", "SPT_QUERY_ANY", "SPT_QUERY_OCCLUDER",
@@ -69,6 +72,76 @@ def whitted_render_ocl(w, h, prims=None, nprims=None, frame=None, counters=False
     check(lib().rtw_render_ocl(C.addressof(prims), nprims, frame.ctypes.data, w, h,
                                C.addressof(cnt) if counters else None))
     return (frame, list(cnt)) if counters else frame
+
+
+def whitted_trace(rays, prims=None, nprims=None, ocl=False, counters=False):
+    """The colour the Whitted tracer computes along each ray (rtw_trace;
+    blocking, numpy): `rays` is float32 [..., 6] (o.xyz, d.xyz; the direction
+    is used as given), e.g. scenes.whitted_camera_rays().  One sub-sample's
+    63-node ray tree and back-accumulation per ray, bit for bit the
+    reference's; ocl: openCLcode.cl's semantics.  Returns (colours float32
+    [n, 3], t float32 [n] -- the root's distance, 1e6 on a miss --, id int32
+    [n] -- the root's primitive or -1), and [traced, shadow, tests, tir] as a
+    fourth item if counters.  scenes.whitted_pack() turns a pixel's
+    sub-sample colours into the frame's word."""
+    if prims is None:
+        prims, nprims = scenes.whitted_scene()
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    n = rays.shape[0]
+    col = np.empty((n, 3), np.float32)
+    t = np.empty(n, np.float32)
+    ids = np.empty(n, np.int32)
+    cnt = (C.c_uint64 * 4)()
+    check(entry("rtw_trace")(C.addressof(prims), nprims, rays.ctypes.data, n, RTW_TRACE_OCL if ocl else 0,
+                             col.ctypes.data, t.ctypes.data, ids.ctypes.data, C.addressof(cnt) if counters else None))
+    return (col, t, ids, list(cnt)) if counters else (col, t, ids)
+
+
+def whitted_trace_async(rays, d_prims, nprims, ocl=False, out=None, counters=None, stream=None):
+    """whitted_trace on device memory (rtw_trace_async): `rays` a contiguous
+    float32 device tensor [n, 6]; `d_prims` a contiguous device tensor of any
+    dtype holding at least nprims 96-byte primitives (a uint8 tensor made from
+    the ctypes array's bytes, say) or a raw device address.  out=(colours, t,
+    id) takes the caller's tensors (float32 [n, 3], float32 [n], int32 [n]; t
+    and id may be None, which leaves that output out); by default all three
+    are allocated.  counters: an int64 device tensor [4] accumulated into.
+    Asynchronous on `stream` (a torch stream or a raw handle; default: torch's
+    current stream), ordered with the level-pass frames as rtw_render_async
+    is; not for graph capture.  Returns (colours, t, id)."""
+    import torch
+    if not (rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 6
+            and rays.is_contiguous()):
+        raise ValueError("whitted_trace_async: rays must be a contiguous float32 device tensor [n, 6]")
+    n = rays.shape[0]
+    if hasattr(d_prims, "data_ptr"):
+        if not (d_prims.is_cuda and d_prims.is_contiguous()
+                and d_prims.numel() * d_prims.element_size() >= C.sizeof(Primitive) * max(int(nprims), 0)):
+            raise ValueError("whitted_trace_async: d_prims must be a contiguous device tensor of at least "
+                             "96 x nprims bytes")
+        d_prims = d_prims.data_ptr()
+    if out is None:
+        col = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+        t = torch.empty(n, dtype=torch.float32, device=rays.device)
+        ids = torch.empty(n, dtype=torch.int32, device=rays.device)
+    else:
+        col, t, ids = out
+        for x, dt, numel in ((col, torch.float32, 3 * n), (t, torch.float32, n), (ids, torch.int32, n)):
+            if (x is None and x is not col) or (x is not None and x.is_cuda and x.dtype == dt and x.numel() >= numel
+                                                  and x.is_contiguous()):
+                continue
+            raise ValueError("whitted_trace_async: out must hold contiguous device tensors: float32 [n, 3], "
+                             "float32 [n] or None, int32 [n] or None")
+    if counters is not None and not (counters.is_cuda and counters.dtype == torch.int64 and counters.numel() == 4
+                                     and counters.is_contiguous()):
+        raise ValueError("whitted_trace_async: counters must be a contiguous int64 device tensor [4]")
+    if stream is None:
+        stream = torch.cuda.current_stream(rays.device)
+    stream = getattr(stream, "cuda_stream", stream)
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    if n:                                                  # (an empty tensor has no address to pass)
+        check(entry("rtw_trace_async")(d_prims, nprims, rays.data_ptr(), n, RTW_TRACE_OCL if ocl else 0, ptr(col),
+                                       ptr(t), ptr(ids), ptr(counters), stream))
+    return col, t, ids
 
 
 def queue_render(w, h, prims=None, nprims=None, counters=False):

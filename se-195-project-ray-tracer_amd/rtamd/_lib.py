@@ -18,6 +18,7 @@ SPT_COST_MAX = 0x200
 SPT_LIST_SET = 0x800
 SPT_QUERY_NEAREST, SPT_QUERY_ANY, SPT_QUERY_OCCLUDER = 0, 1, 2
 RTP_QUERY_NEAREST, RTP_QUERY_SHADOW, RTP_QUERY_OCCLUDER = 0, 1, 2
+RTW_TRACE_OCL = 0x1
 
 # Every symbol include/rt_hip.h declares (checked by tests/test_abi.py).
 EXPORTS = ("rt_last_error", "rt_device_count", "rt_set_device", "rt_release", "rt_cached_bytes",
@@ -34,7 +35,7 @@ EXPORTS = ("rt_last_error", "rt_device_count", "rt_set_device", "rt_release", "r
            "spt_multi_read_frame", "spt_multi_counters", "spt_multi_band_buffers", "spt_render_multi",
            "spt_multi_cache_info", "rtq_render", "rtq_render_async",
            "rtw_prims_create", "rtq_prims_create", "rtp_scene_destroy", "rtw_prims_set_async", "rtq_prims_set_async",
-           "rtp_query_async")
+           "rtp_query_async", "rtw_trace_async", "rtw_trace")
 
 
 class RTError(RuntimeError):
@@ -177,6 +178,9 @@ def lib():
         L.rtw_prims_set_async.argtypes = [vp, vp, i, vp]
         L.rtq_prims_set_async.argtypes = [vp, vp, i, vp]
         L.rtp_query_async.argtypes = [vp, vp, vp, C.c_size_t, i, vp, vp, vp, vp]
+    if hasattr(L, "rtw_trace_async"):
+        L.rtw_trace_async.argtypes = [vp, i, vp, C.c_size_t, i, vp, vp, vp, u64p, vp]
+        L.rtw_trace.argtypes = [vp, i, vp, C.c_size_t, i, vp, vp, vp, u64p]
     _lib = L
     return L
 

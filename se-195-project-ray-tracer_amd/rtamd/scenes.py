@@ -275,6 +275,72 @@ def camera_rays(cam, w, h, x=None, y=None, r1=None, r2=None):
     return out
 
 
+def whitted_camera_rays(w, h, row_begin=20, row_end=None, ocl=False):
+    """The primary rays of the Whitted tracer's frame, as rtw_trace takes
+    them: float32 [row_end - row_begin, w, nsub, 6] rows of (o.xyz, d.xyz).
+    CPU path (raytracer.cpp:278-294, :309, :351-374, :524-526): m_SX and m_SY
+    are the reference's sequential float sums (m_SY from row 20), 3 x 3
+    sub-samples with tx outer and ty inner, rows default [20, h - 70).
+    ocl: raytrace_kernel of openCLcode.cl (:20-23, :66): SX = WX1 + x*DX,
+    SY = WY1 + y*DY, 2 x 2 sub-samples, rows default [20, min(530, h)).
+    Float32 arithmetic, one operation per numpy call, in the reference's
+    order."""
+    if row_end is None:
+        row_end = min(530, h) if ocl else h - 70
+    if row_begin < 20 or row_end > h or row_begin >= row_end:
+        raise ValueError("whitted_camera_rays: rows must satisfy 20 <= row_begin < row_end <= h")
+    WX1, WY1 = f32(-3.0), f32(2.25)
+    DX = (f32(3.0) - WX1) / f32(w)
+    DY = (f32(-2.25) - WY1) / f32(h)
+    if ocl:
+        SX = WX1 + np.arange(w).astype(f32) * DX
+        SY = WY1 + np.arange(row_begin, row_end).astype(f32) * DY
+    else:
+        SX = np.empty(w, f32)
+        sx = WX1
+        for x in range(w):
+            SX[x] = sx
+            sx = f32(sx + DX)
+        sy = f32(WY1 + f32(f32(20) * DY))
+        SYall = np.empty(row_end, f32)
+        for y in range(20, row_end):
+            SYall[y] = sy
+            sy = f32(sy + DY)
+        SY = SYall[row_begin:row_end]
+    side = 2 if ocl else 3
+    out = np.empty((row_end - row_begin, w, side * side, 6), f32)
+    out[..., 0], out[..., 1], out[..., 2] = f32(0.0), f32(0.25), f32(-7.0)
+    for sub in range(side * side):
+        tx, ty = f32(sub // side - 1), f32(sub % side - 1)
+        dx = (SX + DX * tx / f32(2.0)) - f32(0.0)
+        dy = (SY + DY * ty / f32(2.0)) - f32(0.25)
+        dx, dy = np.broadcast_arrays(dx[None, :], dy[:, None])
+        dz = f32(0.0) - f32(-7.0)
+        l = f32(1.0) / np.sqrt(dx * dx + dy * dy + dz * dz)
+        out[:, :, sub, 3], out[:, :, sub, 4], out[:, :, sub, 5] = dx * l, dy * l, dz * l
+    return out
+
+
+def whitted_pack(colors, ocl=False):
+    """Engine_Render's pixel from its sub-samples' colours (raytracer.cpp:
+    513-523; ocl: openCLcode.cl:238-245): colors float32 [..., nsub, 3] ->
+    uint32 [...].  The ordered float32 sum over the sub-samples from 0, x28
+    (ocl: x64), C's (int) conversion -- INT_MIN for a NaN or a value outside
+    int's range, as x86's cvttss2si gives -- each channel clamped to 255 from
+    above only, then r << 16, g << 8 and b added (ocl: ORed) modulo 2^32."""
+    colors = np.asarray(colors, dtype=f32)
+    total = np.zeros(colors.shape[:-2] + (3,), f32)
+    for k in range(colors.shape[-2]):
+        total = total + colors[..., k, :]
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = total * f32(64.0 if ocl else 28.0)
+        ok = np.isfinite(v) & (v < f32(2147483648.0)) & (v >= f32(-2147483648.0))
+        c = np.where(ok, np.trunc(np.where(ok, v, f32(0.0))).astype(np.int64), np.int64(-2147483648))
+    c = np.minimum(c, 255) & 0xffffffff
+    r, g, b = (c[..., 0] << 16) & 0xffffffff, (c[..., 1] << 8) & 0xffffffff, c[..., 2]
+    return ((r | g | b) if ocl else ((r + g + b) & 0xffffffff)).astype(np.uint32)
+
+
 def seeds(width, height, seed=1):
     """AllocateBuffers' seed fill (smallptGPU.cpp:105-110): srand(seed), then
     2*width*height glibc rand() words clamped to >= 2 (spt_seed_fill)."""
