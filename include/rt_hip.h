@@ -703,6 +703,55 @@ int rtq_render(const rtq_primitive *prims, int nprims, uint32_t *pixels, int w, 
 int rtq_render_async(const rtq_primitive *d_prims, int nprims, uint32_t *d_pixels, int w, int h,
                      int row_begin, int row_end, uint64_t *d_counters, void *stream);
 
+/* What colour does the tracer compute along these rays?  d_rays: device
+ * memory, 6 floats per ray (o.xyz d.xyz), used as given: the direction is NOT
+ * normalised.  A queue-tracer pixel is not a sum of per-ray colours: it is
+ * one sequential float chain over every node of all its primaries' trees in
+ * queue order, `acc` carried from one sub-sample into the next
+ * (raytracer_non_OpenCL.c:314-368).  So the rays come in chains: chain c is
+ * rays [c group, (c + 1) group), group = 1..64, nrays a multiple of group.
+ * Per chain (:309-434): acc = 0; for each of its rays in order a Ray with
+ * that origin and direction, weight 1, depth 0, origin_primitive -1, type
+ * ORIGIN, r_index 1 and transparency (1, 1, 1) is pushed and the FIFO drained
+ * -- raytrace (:179-281) per popped ray, its term added to acc by its type
+ * (:351-368), the reflected, then the refracted child pushed while depth < 5
+ * (:370-432).  group = 1 is the colour along one ray; group = 9 over a
+ * frame's camera rays is the frame.
+ *   d_color[3c .. 3c+2]  acc after chain c's last ray has drained;
+ *   d_t[r]               the root raytrace call's *a_dist for ray r, 1e7f on a
+ *                        miss (nullable);
+ *   d_id[r]              its return: the primitive index or -1 (nullable).
+ * The sub-sample grid, the x28 scale, the clamp and the uchar4 pack stay with
+ * the caller (rtamd.scenes.queue_camera_rays / queue_pack restate the
+ * frame's).  d_counters (nullable, device u64[4], accumulated into):
+ * rtq_render's four.  Undefined behaviour is defined as for frames: a ray at
+ * depth < 5 that hits nothing, or hits a light with m_refl or m_refr > 0,
+ * queues no children and is counted in counters[3]; a caller's ray that
+ * leaves the scene has a zero term and d_id -1.  Every float is the
+ * reference's, bit for bit, for any ray and any primitive floats; where the
+ * reference's value is a NaN, some NaN.
+ *
+ * Ordered on `stream` as rtq_render_async is -- serialised with the other
+ * level-pass frames on the device, whose arena it shares -- but on that one
+ * stream only.  The chains run in slabs of whole chains, at most 6 M rays
+ * each, one after the other (RT_QUEUE_TRACE_SLAB=<rays>, rounded up to whole
+ * chains and to 64 chains, forces small ones; RT_QUEUE_POOL_CAP and
+ * RT_QUEUE_EXACT_ALL apply as to frames: test hooks, the same bits).  A trace
+ * of N rays caches no more device memory than a frame of N trees.  NOT
+ * promised to be graph-capturable: the arena may grow, and sizing the record
+ * pool reads a host flag.  nrays == 0 is RT_OK and launches nothing.  The
+ * outputs must not alias the inputs; an output that is not asked for is not
+ * written.  RT_ERR_INVALID before any device work: a null d_prims, d_rays or
+ * d_color; nprims outside 1..64; group outside 1..64; nrays not a multiple of
+ * group; nrays above INT32_MAX. */
+int rtq_trace_async(const rtq_primitive *d_prims, int nprims, const float *d_rays, size_t nrays, int group,
+                    float *d_color, float *d_t, int *d_id, uint64_t *d_counters, void *stream);
+/* Blocking, host buffers (color: 3 floats per chain); counters (nullable,
+ * host u64[4]) receives this call's counts.  The device copies are the call's
+ * own allocation, freed before it returns. */
+int rtq_trace(const rtq_primitive *prims, int nprims, const float *rays, size_t nrays, int group,
+              float *color, float *t, int *id, uint64_t *counters);
+
 /* ------------------------------------------------------------ level-pass tracers, ray queries */
 /* What does this ray hit, and is this point shadowed?  Caller-supplied rays
  * against the primitives of the Whitted tracer (raytracer3.0.06) or of the

@@ -704,6 +704,74 @@ final_kernel(QArgs A, int row_end, uint32_t *__restrict__ out, unsigned long lon
     if (COUNT) flush_counters<4>(counters, cnt);
 }
 
+// Where a chain of trees -- a frame's pixel, or a chain of the caller's rays
+// (rtq_trace_async) -- comes from and goes to: fix_kernel's View.  nsub():
+// trees per chain; begin(): the sum of the chain's leading childless trees and
+// the first recorded one, as the root kernel left them; root(): the root ray
+// of tree `sub` of the chain; store(): the finished sum.
+struct CameraView {
+    float DX, DY;
+    uint32_t *__restrict__ out;
+    __device__ __forceinline__ int nsub() const { return NSUB; }
+    __device__ __forceinline__ int begin(const QArgs &A, int pix, float &ax, float &ay, float &az) const
+    {
+        const float4 ps = A.psum[pix];
+        ax = ps.x; ay = ps.y; az = ps.z;
+        return __float_as_int(ps.w);
+    }
+    __device__ __forceinline__ Node root(const QArgs &A, int sub, int pix) const
+    {
+        return primary(sub, pix % A.w, slab_row(A, pix / A.w), DX, DY);
+    }
+    __device__ __forceinline__ void store(const QArgs &A, int pix, float ax, float ay, float az) const
+    {
+        const int x = pix % A.w, y = slab_row(A, pix / A.w);
+        out[(size_t)y * A.w + x] = pack_pixel(ax, ay, az);
+    }
+};
+
+// The caller's ray as a queued ORIGIN ray (:320-339 with the caller's origin
+// and direction, used as given).
+__device__ __forceinline__ Node caller_root(const float *p)
+{
+    Node n;
+    n.r.o = mk(p[0], p[1], p[2]);
+    n.r.d = mk(p[3], p[4], p[5]);
+    n.w = 1.0f;
+    n.tr = mk(1.f, 1.f, 1.f);
+    n.origin = -1;
+    n.type = 0;
+    n.rcode = 0;
+    return n;
+}
+
+// A trace call's arena keeps no float4 per chain: the leading sum lives in the
+// caller's colour array until the chain is finished, and the first recorded
+// tree is a byte per chain in psum's place (group <= 64).
+__device__ __forceinline__ unsigned char *chain_first(const QArgs &A) { return (unsigned char *)A.psum; }
+
+struct RayView {
+    const float *__restrict__ rays;      // the slab's first ray: chain c is rays [c group, (c + 1) group)
+    float *color;                        // the slab's first chain's colour
+    int group;
+    __device__ __forceinline__ int nsub() const { return group; }
+    __device__ __forceinline__ int begin(const QArgs &A, int c, float &ax, float &ay, float &az) const
+    {
+        const float *o = color + 3 * (size_t)c;
+        ax = o[0]; ay = o[1]; az = o[2];
+        return chain_first(A)[c];
+    }
+    __device__ __forceinline__ Node root(const QArgs &, int sub, int c) const
+    {
+        return caller_root(rays + 6 * ((size_t)c * group + sub));
+    }
+    __device__ __forceinline__ void store(const QArgs &, int c, float ax, float ay, float az) const
+    {
+        float *o = color + 3 * (size_t)c;
+        o[0] = ax; o[1] = ay; o[2] = az;
+    }
+};
+
 // Node `j` (heap index) of a tree re-derived from its root: the ancestors'
 // rays re-traced (uncounted; their spec terms do not shape the children),
 // node j traced exactly.  false if node j does not exist.
@@ -729,10 +797,11 @@ __device__ bool derive_node(const Scene &S, const Node &root, int j, Node &n, Hi
 // The pixels final_kernel skipped: the chain over all nine trees, recorded
 // trees from their records, flagged trees node by node in heap order, each
 // node's ray re-derived from the root and traced exactly.  Waves take listed
-// pixels (or, past the list's capacity, 32-pixel words of pixbits).
-template <bool COUNT>
+// pixels (or, past the list's capacity, 32-pixel words of pixbits).  A trace
+// call's "pixels" are its chains, its root rays the caller's (View).
+template <bool COUNT, class View>
 __global__ void __launch_bounds__(64)
-fix_kernel(QArgs A, float DX, float DY, uint32_t *__restrict__ out, unsigned long long *__restrict__ counters)
+fix_kernel(QArgs A, View view, unsigned long long *__restrict__ counters)
 {
     const int nfix = lq::counter(A, C_FIX);
     if (nfix == 0) return;
@@ -760,16 +829,15 @@ fix_kernel(QArgs A, float DX, float DY, uint32_t *__restrict__ out, unsigned lon
             const int bit = __builtin_ctz(bits);
             bits &= bits - 1u;
             const int pix = scan ? (it << 5) + bit : A.fixlist[it];
-            const int x = pix % A.w, y = slab_row(A, pix / A.w);
-            const float4 ps = A.psum[pix];
-            float ax = ps.x, ay = ps.y, az = ps.z;
-            for (int sub = __float_as_int(ps.w); sub < NSUB; sub++) {
+            float ax, ay, az;
+            const int nsub = view.nsub();
+            for (int sub = view.begin(A, pix, ax, ay, az); sub < nsub; sub++) {
                 const int tree = sub * A.npix + pix;
                 if (!tree_flagged(A, tree)) {
                     fold_tree<COUNT, 64>(A, tree, ring, ax, ay, az, cnt);
                     continue;
                 }
-                const Node root = primary(sub, x, y, DX, DY);
+                const Node root = view.root(A, sub, pix);
                 unsigned long long todo = 1ull;
                 while (todo) {
                     const int j = __builtin_ctzll(todo);
@@ -788,7 +856,182 @@ fix_kernel(QArgs A, float DX, float DY, uint32_t *__restrict__ out, unsigned lon
                     if (f & 2) todo |= 1ull << (2 * j + 2);
                 }
             }
-            out[(size_t)y * A.w + x] = pack_pixel(ax, ay, az);
+            view.store(A, pix, ax, ay, az);
+        }
+    }
+    if (COUNT) flush_counters<4>(counters, cnt);
+}
+
+// ---------------------------------------------------------------------------
+// The caller's rays as trees (rtq_trace_async).  A chain of `group`
+// consecutive rays is what a pixel's nine primaries are to a frame: one
+// accumulator, each ray's tree added node by node in queue order before the
+// next ray is pushed (:314-368).  Tree j * nchains + c is ray j of chain c
+// (the frame: sub * npix + pix), so A.npix = the slab's chains, and
+// level_kernel, queue_children, the pool and the flag words run unchanged;
+// these two kernels replace root_kernel and final_kernel, and fix_kernel reads
+// a flagged tree's root from the ray array (RayView).
+
+// LDS traffic of one wave to itself: the stores of all lanes before the loads
+// of any (a wave's LDS operations execute in order; this keeps the compiler
+// from moving them across).
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+constexpr int STAGE_ROW = 12;     // floats per lane in the root kernel's stage: two rays
+
+// `nrows` chains' SEG floats each (SEG / 6 consecutive rays of every chain,
+// `pitch` floats from one chain's to the next's) from src into the wave's
+// stage: lane l takes floats l, l + 64, ... of the rows laid end to end, so a
+// load instruction reads runs of SEG consecutive floats.  Three loads in
+// flight per lane: unrolled by 6 or 12 their addresses cost the kernel 76-212
+// B/lane of scratch at its 72 VGPRs (by 3: 0 uncounted, 40 counted).
+template <int SEG>
+__device__ __forceinline__ void stage_rows(float *__restrict__ st, const float *__restrict__ src, int pitch, int nrows)
+{
+    const int lane = __lane_id();
+#pragma unroll 3
+    for (int k = 0; k < SEG; k++) {
+        const int i = k * 64 + lane;
+        const int row = i / SEG, off = i % SEG;
+        if (row < nrows) st[row * STAGE_ROW + off] = src[row * pitch + off];
+    }
+}
+
+// Level 0: a lane per chain, its rays in order, two at a time as root_kernel
+// takes a pixel's sub-samples (nearest_n<2>), with the same rule: while the
+// chain's trees have no children they are summed here, from the first one
+// with children (or an uncertified term) on they are recorded.  A lane's rays
+// lie 24 group bytes from its neighbour's, so each round's two rays per chain
+// come through LDS: the wave reads the 48-byte runs of its 64 chains with
+// consecutive lanes on consecutive floats (one ray per chain and group = 1:
+// plain consecutive floats) and each lane reads its two rays back.  A lane
+// past the slab's chains runs an all-NaN ray through the nearest-hit loop (it
+// takes nothing and asks for no exact-sqrt redo) and neither shades, queues,
+// records nor counts.  d_t and d_id are the root hit's.  The leading sum goes
+// to the chain's colour and the first recorded tree to chain_first for
+// trace_final_kernel / fix_kernel.
+#ifndef RT_Q_TRACE_ROOT_MINWAVES
+#define RT_Q_TRACE_ROOT_MINWAVES 7      // what the block's LDS (scene + stage: 22,304 B) leaves room for
+#endif
+template <bool COUNT, bool UNCERT>
+__global__ void __launch_bounds__(256, RT_Q_TRACE_ROOT_MINWAVES)
+trace_root_kernel(QArgs A, const float *__restrict__ rays, int group, float *__restrict__ color,
+                  float *__restrict__ t_out, int *__restrict__ id_out, unsigned long long *__restrict__ counters)
+{
+    __shared__ Scene S;
+    __shared__ __attribute__((aligned(16))) float stage[4][64 * STAGE_ROW];
+    load_scene(S, A.scene);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = blockIdx.x * 256 + wave * 64;              // the wave's first chain
+    const int nrows = min(64, A.npix - c0);
+    if (nrows <= 0) return;                                   // (a whole wave, after the block's only barrier)
+    const int c = c0 + lane;
+    const bool active = lane < nrows;
+    const int wave_id = (blockIdx.x << 2) + wave;
+    float *st = stage[wave];
+    const float *__restrict__ src0 = rays + 6 * (size_t)c0 * group;
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    int kfirst = group;
+#pragma unroll 1
+    for (int s0 = 0; s0 < group; s0 += 2) {
+        const bool two = s0 + 1 < group;
+        wave_lds_sync();                                      // (the last round's reads are done)
+        if (two) stage_rows<12>(st, src0 + 6 * s0, 6 * group, nrows);
+        else stage_rows<6>(st, src0 + 6 * s0, 6 * group, nrows);
+        wave_lds_sync();
+        // (the rays are read again from the stage when they are shaded, as
+        // root_kernel rebuilds its primaries: not held across the hit loops)
+        const float nan = __builtin_nanf("");
+        ray3 rr[2];
+        rr[0].o = rr[0].d = mk(nan, nan, nan);
+        if (active) rr[0] = caller_root(st + lane * STAGE_ROW).r;
+        rr[1] = rr[0];
+        if (active && two) rr[1] = caller_root(st + lane * STAGE_ROW + 6).r;
+        float dd[2];
+        int pp[2], rs[2];
+        if (two) {
+            prims::nearest_n<2, NearestTraits>(S, rr, dd, pp, rs);
+        } else {
+            const ray3 r1[1] = {rr[0]};
+            float d1[1];
+            int p1[1], q1[1];
+            prims::nearest_n<1, NearestTraits>(S, r1, d1, p1, q1);
+            dd[0] = d1[0]; pp[0] = p1[0]; rs[0] = q1[0];
+        }
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int sub = s0 + j;
+            if (sub >= group) break;
+            Node n;
+            Hit h;
+            int f = 0;
+            if (active) {
+                n = caller_root(st + lane * STAGE_ROW + 6 * j);
+                h = shade_hit<COUNT, false, UNCERT>(S, n.r, dd[j], pp[j], rs[j]);
+                f = child_flags(S, n, h);
+            }
+            const int tree = sub * A.npix + c;
+            const int2 ch = queue_children(A, S, 0, 0, wave_id, active, f, n, h, tree, 0);
+            if (active) {
+                const size_t r = (size_t)c * group + sub;
+                if (t_out) t_out[r] = h.dist;
+                if (id_out) id_out[r] = h.prim;
+                const v3 tc = term(S, n, h);    // weight 1, type ORIGIN: ray_col * 1.0f
+                const unsigned cw = h.cnt | ((f & 4) ? CNT_UB : 0u);
+                if (kfirst == group && !(f & 3) && !h.amb) {
+                    ax += tc.x; ay += tc.y; az += tc.z;
+                    if (COUNT) {
+                        cnt[0] += 1; cnt[1] += (cw >> 16) & 0xff; cnt[2] += cw & 0xffff; cnt[3] += cw >> 24;
+                    }
+                } else {
+                    if (kfirst == group) kfirst = sub;
+                    A.rcol[tree] = make_float4(tc.x, tc.y, tc.z, __uint_as_float(cw));
+                    A.rchild[tree] = ch;
+                    if (h.amb) flag_tree(A, tree);
+                }
+            }
+        }
+    }
+    if (active) {
+        float *o = color + 3 * (size_t)c;
+        o[0] = ax; o[1] = ay; o[2] = az;
+        chain_first(A)[c] = (unsigned char)kfirst;
+    }
+    if (COUNT) flush_counters<4>(counters, cnt);
+}
+
+// A chain's recorded trees folded in order onto its leading sum, for every
+// chain whose trees' records are complete and exact (the others: fix_kernel).
+// The next tree's root record is in flight while one tree is folded.
+template <bool COUNT>
+__global__ void __launch_bounds__(256)
+trace_final_kernel(QArgs A, int group, float *__restrict__ color, unsigned long long *__restrict__ counters)
+{
+    __shared__ int ring[RING][256];
+    const int c = blockIdx.x * 256 + (int)threadIdx.x;
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    if (c < A.npix && !pix_flagged(A, c)) {
+        const int kf = chain_first(A)[c];
+        if (kf < group) {                                     // (else the root kernel's sum is the chain's)
+            float *o = color + 3 * (size_t)c;
+            float ax = o[0], ay = o[1], az = o[2];
+            float4 c0 = A.rcol[kf * A.npix + c];
+            int2 ch = A.rchild[kf * A.npix + c];
+            for (int j = kf; j < group; j++) {
+                const int next = min(j + 1, group - 1) * A.npix + c;
+                const float4 n0 = A.rcol[next];
+                const int2 nch = A.rchild[next];
+                fold_tree_from<COUNT, 256>(A, c0, ch, ring, ax, ay, az, cnt);
+                c0 = n0;
+                ch = nch;
+            }
+            o[0] = ax; o[1] = ay; o[2] = az;
         }
     }
     if (COUNT) flush_counters<4>(counters, cnt);
@@ -816,13 +1059,19 @@ constexpr int SLOT_Q2 = 10;
 constexpr long long SLAB_TREES = 6000000;
 constexpr double POOL_FRAC = 0.8;
 
-int arena(rtrt::DeviceState &st, int slot, int w, int rows, rt::queue::QArgs *A)
+// A trace call's arena (rtq_trace_async: w chains, one row, nsub = group) has a
+// byte per chain where a frame has a float4 per pixel (chain_first) and learns
+// its pool fraction under its own key, so a trace never moves a frame size's
+// fraction; with the same fraction it is no larger than the arena of a frame
+// of as many trees.
+int arena(rtrt::DeviceState &st, int slot, int w, int rows, rt::queue::QArgs *A, int nsub = rt::queue::NSUB,
+          int pool_key = rtrt::POOL_QUEUE, size_t psum_each = 16)
 {
     using namespace rt::queue;
-    const size_t T = (size_t)w * rows * NSUB;
+    const size_t T = (size_t)w * rows * nsub;
     if (T > (size_t)0x7fffffff / 2) return rtrt::fail(RT_ERR_INVALID, "rtq: frame too large");
     int *ovf = nullptr;
-    size_t P = (size_t)(T * rtrt::pool_fraction(st, rtrt::POOL_QUEUE, (long long)T, POOL_FRAC, &ovf));
+    size_t P = (size_t)(T * rtrt::pool_fraction(st, pool_key, (long long)T, POOL_FRAC, &ovf));
     if (const char *e = getenv("RT_QUEUE_POOL_CAP")) {      // test hook: exercises the overflow path
         const long long v = atoll(e);
         if (v > 0 && (size_t)v < P) P = (size_t)v;
@@ -835,7 +1084,7 @@ int arena(rtrt::DeviceState &st, int slot, int w, int rows, rt::queue::QArgs *A)
         a.take(A->scene, sizeof(Scene));
         a.take(A->rcol, T * 16);
         a.take(A->rchild, T * 8);
-        a.take(A->psum, npix * 16);
+        a.take(A->psum, npix * psum_each);
         a.take(A->fixbits, FB);
         a.take(A->pixbits, PB);
         a.take(A->fixlist, FC * 4);
@@ -865,8 +1114,101 @@ int launch(const rt::queue::QArgs &A, int w, int rows, int row_end, float DX, fl
     for (int L = 1; L < LEVELS; L++)
         hipLaunchKernelGGL((level_kernel<COUNT, UNCERT>), dim3(level_blocks), block, 0, s, A, L);
     hipLaunchKernelGGL(final_kernel<COUNT>, tiles, block, 0, s, A, row_end, d_px, cnt);
-    hipLaunchKernelGGL(fix_kernel<COUNT>, dim3(256), dim3(64), 0, s, A, DX, DY, d_px, cnt);
+    hipLaunchKernelGGL((fix_kernel<COUNT, CameraView>), dim3(256), dim3(64), 0, s, A, CameraView{DX, DY, d_px}, cnt);
     return rtrt::check_launch("rtq kernels");
+}
+
+template <bool COUNT, bool UNCERT>
+int launch_trace(const rt::queue::QArgs &A, const float *d_rays, int group, float *d_color, float *d_t, int *d_id,
+                 unsigned long long *cnt, hipStream_t s)
+{
+    using namespace rt::queue;
+    static const int level_blocks = rtrt::resident_blocks(level_kernel<COUNT, UNCERT>);
+    const dim3 grid((A.npix + 255) / 256), block(256);
+    // (a small batch: no more level blocks than its pool has pages for)
+    const int lblocks = (int)std::min<long long>(level_blocks, ((long long)A.pool + 255) / 256);
+    hipLaunchKernelGGL((trace_root_kernel<COUNT, UNCERT>), grid, block, 0, s, A, d_rays, group, d_color, d_t, d_id, cnt);
+    for (int L = 1; L < LEVELS; L++)
+        hipLaunchKernelGGL((level_kernel<COUNT, UNCERT>), dim3(lblocks), block, 0, s, A, L);
+    hipLaunchKernelGGL(trace_final_kernel<COUNT>, grid, block, 0, s, A, group, d_color, cnt);
+    hipLaunchKernelGGL((fix_kernel<COUNT, RayView>), dim3(256), dim3(64), 0, s, A, RayView{d_rays, d_color, group}, cnt);
+    return rtrt::check_launch("rtq trace kernels");
+}
+
+// Chains per slab of a trace call: at most SLAB_TREES trees, whole chains, a
+// multiple of 64 of them (whole waves of the root kernel).
+// RT_QUEUE_TRACE_SLAB=<rays> (test hook, rounded up to whole chains and to 64
+// chains) forces small slabs.
+long long trace_slab_chains(int group)
+{
+    long long slab = std::max<long long>(SLAB_TREES / group / 64, 1) * 64;
+    if (const char *e = getenv("RT_QUEUE_TRACE_SLAB")) {
+        const long long v = atoll(e);
+        if (v > 0) slab = std::min(slab, ((v + group - 1) / group + 63) / 64 * 64);
+    }
+    return slab;
+}
+
+// The colour the tracer computes along the caller's chains of rays: slab
+// after slab on the caller's stream, under the frame bracket (the arena is
+// the frames').
+int trace_async(const rtq_primitive *d_prims, int nprims, const float *d_rays, size_t nrays, int group, float *d_color,
+                float *d_t, int *d_id, uint64_t *d_counters, void *stream)
+{
+    rtrt::DeviceState *st;
+    int rc = rtrt::state(&st);
+    if (rc) return rc;
+    std::lock_guard<std::recursive_mutex> lk(st->mu);
+    hipStream_t s = (hipStream_t)stream;
+    rtrt::Frame frame(*st, s, "rtq_trace_async");
+    if ((rc = frame.begin())) return rc;
+    const long long nchains = (long long)(nrays / (size_t)group), slab = trace_slab_chains(group);
+    rt::queue::QArgs A;
+    if ((rc = arena(*st, SLOT_Q, (int)std::min(nchains, slab), 1, &A, group, rtrt::POOL_QUEUE_TRACE, 1))) return rc;
+    A.row_begin = 0;
+    A.row_stride = 1;
+    unsigned long long *cnt = (unsigned long long *)d_counters;
+    const char *ex = getenv("RT_QUEUE_EXACT_ALL");
+    for (long long first = 0; first < nchains; first += slab) {
+        const int n = (int)std::min(slab, nchains - first);
+        A.w = A.npix = n;
+        A.ntrees = n * group;
+        const int nz0 = rtrt::words16(sizeof(int) * rt::queue::C_TOTAL * rt::lq::CSTRIDE);
+        const int nz1 = rtrt::words16(sizeof(unsigned) * (((size_t)A.ntrees + 31) / 32));
+        const int nz2 = rtrt::words16(sizeof(unsigned) * (((size_t)A.npix + 31) / 32));
+        const int pblocks = std::min(1024, std::max(1, (nz0 + nz1 + nz2 + 255) / 256));
+        hipLaunchKernelGGL(rt::queue::prep_kernel, dim3(pblocks), dim3(256), 0, s, first == 0 ? d_prims : nullptr,
+                           nprims, (rt::queue::Scene *)A.scene, (uint4 *)A.count, nz0, (uint4 *)A.fixbits, nz1,
+                           (uint4 *)A.pixbits, nz2);
+        const size_t r0 = (size_t)first * group;
+        const float *r = d_rays + 6 * r0;
+        float *c = d_color + 3 * (size_t)first, *t = d_t ? d_t + r0 : nullptr;
+        int *id = d_id ? d_id + r0 : nullptr;
+        if (ex && *ex == '1')
+            rc = cnt ? launch_trace<true, true>(A, r, group, c, t, id, cnt, s)
+                     : launch_trace<false, true>(A, r, group, c, t, id, cnt, s);
+        else
+            rc = cnt ? launch_trace<true, false>(A, r, group, c, t, id, cnt, s)
+                     : launch_trace<false, false>(A, r, group, c, t, id, cnt, s);
+        if (rc) return rc;
+    }
+    return frame.end();
+}
+
+// What rtq_trace_async and rtq_trace refuse before any device work.
+int trace_args(const char *who, const void *prims, int nprims, const void *rays, size_t nrays, int group,
+               const void *color)
+{
+    char msg[160];
+    const char *why = nullptr;
+    if (!prims || !rays || !color) why = "null primitives, rays or colour output";
+    else if (nprims < 1 || nprims > rt::queue::MAXP) why = "nprims outside 1..64";
+    else if (group < 1 || group > 64) why = "group outside 1..64";
+    else if (nrays % (size_t)group) why = "nrays is not a multiple of group";
+    else if (nrays > (size_t)INT32_MAX) why = "too many rays";
+    if (!why) return RT_OK;
+    snprintf(msg, sizeof(msg), "%s: %s", who, why);
+    return rtrt::fail(RT_ERR_INVALID, msg);
 }
 
 }  // namespace
@@ -944,4 +1286,56 @@ extern "C" int rtq_render(const rtq_primitive *prims, int nprims, uint32_t *pixe
                                  [&](const rtq_primitive *d_prims, uint32_t *d_px, uint64_t *d_cnt, hipStream_t s) {
                                      return rtq_render_async(d_prims, nprims, d_px, w, h, 0, h, d_cnt, s);
                                  });
+}
+
+extern "C" int rtq_trace_async(const rtq_primitive *d_prims, int nprims, const float *d_rays, size_t nrays, int group,
+                               float *d_color, float *d_t, int *d_id, uint64_t *d_counters, void *stream)
+{
+    int rc = trace_args("rtq_trace_async", d_prims, nprims, d_rays, nrays, group, d_color);
+    if (rc || nrays == 0) return rc;
+    return trace_async(d_prims, nprims, d_rays, nrays, group, d_color, d_t, d_id, d_counters, stream);
+}
+
+// Blocking, host buffers.  The device copies live in one allocation of the
+// call's own, freed before it returns: the cached staging slots stay what the
+// frames made them, so a trace caches no more than its arena.
+extern "C" int rtq_trace(const rtq_primitive *prims, int nprims, const float *rays, size_t nrays, int group,
+                         float *color, float *t, int *id, uint64_t *counters)
+{
+    int rc = trace_args("rtq_trace", prims, nprims, rays, nrays, group, color);
+    if (rc) return rc;
+    if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0;
+    if (nrays == 0) return RT_OK;
+    rtrt::DeviceState *st;
+    if ((rc = rtrt::state(&st))) return rc;
+    std::lock_guard<std::recursive_mutex> lk(st->mu);
+    const auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t nchains = nrays / (size_t)group;
+    const size_t o_rays = r256(sizeof(rtq_primitive) * (size_t)nprims), o_col = o_rays + r256(24 * nrays),
+                 o_t = o_col + r256(12 * nchains), o_id = o_t + r256(4 * nrays), o_cnt = o_id + r256(4 * nrays),
+                 total = o_cnt + 256;
+    char *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, total);
+    if (e != hipSuccess) return rtrt::fail_hip(e, "rtq_trace hipMalloc");
+    hipStream_t s = st->stream;
+    e = hipMemcpyAsync(d, prims, sizeof(rtq_primitive) * (size_t)nprims, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + o_rays, rays, 24 * nrays, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && counters) e = hipMemsetAsync(d + o_cnt, 0, 4 * sizeof(uint64_t), s);
+    if (e != hipSuccess) rc = rtrt::fail_hip(e, "rtq_trace H2D");
+    if (!rc)
+        rc = trace_async((const rtq_primitive *)d, nprims, (const float *)(d + o_rays), nrays, group,
+                         (float *)(d + o_col), t ? (float *)(d + o_t) : nullptr, id ? (int *)(d + o_id) : nullptr,
+                         counters ? (uint64_t *)(d + o_cnt) : nullptr, s);
+    if (!rc) {
+        e = hipMemcpyAsync(color, d + o_col, 12 * nchains, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && t) e = hipMemcpyAsync(t, d + o_t, 4 * nrays, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && id) e = hipMemcpyAsync(id, d + o_id, 4 * nrays, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && counters)
+            e = hipMemcpyAsync(counters, d + o_cnt, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) rc = rtrt::fail_hip(e, "rtq_trace D2H");
+    }
+    e = hipStreamSynchronize(s);          // (also before the free: the kernels read d)
+    if (e != hipSuccess && !rc) rc = rtrt::fail_hip(e, "rtq_trace sync");
+    (void)hipFree(d);
+    return rc;
 }

@@ -116,7 +116,7 @@ int state(DeviceState **out)
             delete st;
             return fail_hip(e, "hipEventCreate");
         }
-        e = hipHostMalloc((void **)&st->pool_ovf, (POOL_FITS + POOL_TRACE_BUCKETS) * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
+        e = hipHostMalloc((void **)&st->pool_ovf, POOL_OVF_FLAGS * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
         if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&st->pool_ovf_dev, st->pool_ovf, 0);
         if (e != hipSuccess) {
             (void)hipEventDestroy(st->wf_done);
@@ -125,7 +125,7 @@ int state(DeviceState **out)
             delete st;
             return fail_hip(e, "hipHostMalloc");
         }
-        memset(st->pool_ovf, 0, (POOL_FITS + POOL_TRACE_BUCKETS) * sizeof(int));
+        memset(st->pool_ovf, 0, POOL_OVF_FLAGS * sizeof(int));
         g_states[dev] = st;
         // The second stream (two-slab level-pass frames) is created with the
         // state, not at its first use: created mid-run it ran the 1080p
@@ -177,19 +177,22 @@ static double first_fraction(double initial)
 
 double pool_fraction(DeviceState &st, int which, long long trees, double initial, int **flag_dev)
 {
-    if (which == POOL_WHITTED_TRACE) {
+    if (which == POOL_WHITTED_TRACE || which == POOL_QUEUE_TRACE) {
+        const int k = which == POOL_QUEUE_TRACE ? 1 : 0;
+        double *frac = st.trace_frac[k];
         int b = 0;
         while (b < POOL_TRACE_BUCKETS - 1 && (1LL << b) < trees) b++;
-        volatile int *flag = st.pool_ovf + POOL_FITS + b;
-        if (st.trace_frac[b] == 0.0) {
-            st.trace_frac[b] = first_fraction(initial);
+        const int slot = POOL_FITS + k * POOL_TRACE_BUCKETS + b;
+        volatile int *flag = st.pool_ovf + slot;
+        if (frac[b] == 0.0) {
+            frac[b] = first_fraction(initial);
         } else if (*flag) {
-            const double f = st.trace_frac[b] * 1.25;
-            st.trace_frac[b] = f < POOL_FRAC_MAX ? f : POOL_FRAC_MAX;
+            const double f = frac[b] * 1.25;
+            frac[b] = f < POOL_FRAC_MAX ? f : POOL_FRAC_MAX;
         }
         *flag = 0;
-        *flag_dev = st.pool_ovf_dev + POOL_FITS + b;
-        return st.trace_frac[b];
+        *flag_dev = st.pool_ovf_dev + slot;
+        return frac[b];
     }
     int i = 0;
     while (i < POOL_FITS && !(st.pool_fit[i].which == which && st.pool_fit[i].trees == trees)) i++;

@@ -36,7 +36,8 @@ struct DeviceState {
     hipEvent_t wf_done = nullptr;
     bool wf_pending = false;
     // Record pools of the level passes (POOL_WHITTED, POOL_QUEUE, and
-    // POOL_WHITTED_TRACE for rtw_trace_async's slabs of caller rays) as a
+    // POOL_WHITTED_TRACE / POOL_QUEUE_TRACE for rtw_trace_async's and
+    // rtq_trace_async's slabs of caller rays) as a
     // fraction of a slab's trees, learnt per (pass, slab size).  A frame whose
     // nodes did not all fit (the trees left over are re-evaluated exactly by
     // the fixup kernels, one lane per tree: correct but slow) raises its
@@ -46,22 +47,24 @@ struct DeviceState {
     struct PoolFit { int which = -1; long long trees = 0; double frac = 0.0; };
     PoolFit pool_fit[16];
     int pool_fit_next = 0;
-    int *pool_ovf = nullptr;           // host-mapped [POOL_FITS + POOL_TRACE_BUCKETS]
+    int *pool_ovf = nullptr;           // host-mapped [POOL_OVF_FLAGS]
     int *pool_ovf_dev = nullptr;       // its device address
-    // rtw_trace_async's fractions (POOL_WHITTED_TRACE): ray batches come in any
-    // size, so they are kept apart from pool_fit -- a trace can neither evict
-    // nor reset a frame size's entry -- in a table indexed by the slab's ray
-    // count rounded up to a power of two (bucket b: 2^(b-1) < rays <= 2^b;
-    // 0: not used yet); flag b is pool_ovf[POOL_FITS + b].  No eviction, so no
-    // wait for the frame in flight either.
-    double trace_frac[32] = {};
+    // rtw_trace_async's and rtq_trace_async's fractions (POOL_WHITTED_TRACE,
+    // POOL_QUEUE_TRACE): ray batches come in any size, so they are kept apart
+    // from pool_fit -- a trace can neither evict nor reset a frame size's entry
+    // -- in a table per tracer indexed by the slab's ray count rounded up to a
+    // power of two (bucket b: 2^(b-1) < rays <= 2^b; 0: not used yet); flag b of
+    // table k (0 Whitted, 1 queue) is pool_ovf[POOL_FITS + k * POOL_TRACE_BUCKETS
+    // + b].  No eviction, so no wait for the frame in flight either.
+    double trace_frac[2][32] = {};
     // A second stream for the level pass's concurrent slabs (aux_stream):
     // forked from and joined back to the caller's stream by events.
     hipStream_t aux = nullptr;
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
 };
 
-constexpr int POOL_WHITTED = 0, POOL_QUEUE = 1, POOL_WHITTED_TRACE = 2, POOL_FITS = 16, POOL_TRACE_BUCKETS = 32;
+constexpr int POOL_WHITTED = 0, POOL_QUEUE = 1, POOL_WHITTED_TRACE = 2, POOL_QUEUE_TRACE = 3, POOL_FITS = 16,
+              POOL_TRACE_BUCKETS = 32, POOL_OVF_FLAGS = POOL_FITS + 2 * POOL_TRACE_BUCKETS;
 constexpr double POOL_FRAC_MAX = 8.0;
 
 // Records msg (plus the HIP error string) for rt_last_error(); returns code.
@@ -76,7 +79,8 @@ int scratch(DeviceState &st, int slot, size_t bytes, void **out);
 // Pool fraction of level pass `which` for the next frame of `trees` trees
 // per slab (starts at `initial`; grown after an overflowed frame of that
 // size) and, in *flag_dev, the device address of that entry's overflow flag.
-// POOL_WHITTED_TRACE: per power-of-two bucket of `trees` (DeviceState::trace_frac).
+// POOL_WHITTED_TRACE, POOL_QUEUE_TRACE: per power-of-two bucket of `trees`
+// (DeviceState::trace_frac).
 double pool_fraction(DeviceState &st, int which, long long trees, double initial, int **flag_dev);
 // The state's second stream and its fork / join events (created on first use).
 int aux_stream(DeviceState &st);

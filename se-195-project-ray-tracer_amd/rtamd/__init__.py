@@ -20,7 +20,9 @@ what the tests, bench.py and __graft_entry__ drive.
                primitives (rtp_query_async): nearest hit, shadowed or not,
                the first occluder;
                whitted_trace() / whitted_trace_async(): the colour the Whitted
-               tracer computes along the caller's rays (rtw_trace_async)
+               tracer computes along the caller's rays (rtw_trace_async);
+               queue_trace() / queue_trace_async(): the queue tracer's, along
+               the caller's chains of rays (rtq_trace_async)
 """
 import ctypes as C
 
@@ -35,7 +37,7 @@ from ._lib import (Camera, Float4, Primitive, QPrimitive, RTError, Sphere, Vec3,
 
 __all__ = ["Camera", "Primitive", "QPrimitive", "Float4", "Sphere", "Vec3", "RTError", "scenes", "lib", "check",
            "device_count", "set_device", "whitted_render", "whitted_trace", "whitted_trace_async",
-           "RTW_TRACE_OCL", "queue_render", "SmallptFrame", "SmallptScene",
+           "RTW_TRACE_OCL", "queue_render", "queue_trace", "queue_trace_async", "SmallptFrame", "SmallptScene",
            "SmallptMulti", "SmallptDeviceFrame", "PrimScene",
            "SPT_PATH_TRACING", "SPT_DIRECT_LIGHTING", "SPT_COUNT_RAYS", "SPT_COST_MAX", "SPT_LIST_SET",
            "SPT_QUERY_NEAREST", "SPT_QUERY_ANY", "SPT_QUERY_OCCLUDER",
@@ -155,6 +157,81 @@ def queue_render(w, h, prims=None, nprims=None, counters=False):
     check(lib().rtq_render(C.addressof(prims), nprims, frame.ctypes.data, w, h,
                            C.addressof(cnt) if counters else None))
     return (frame, list(cnt)) if counters else frame
+
+
+def queue_trace(rays, prims=None, nprims=None, group=1, counters=False):
+    """The colour the queue tracer computes along the caller's rays (rtq_trace;
+    blocking, numpy): `rays` is float32 [..., 6] (o.xyz, d.xyz; the direction
+    is used as given), e.g. scenes.queue_camera_rays().  `group` (1..64)
+    consecutive rays form a chain: one accumulator that every node of their
+    trees is added to in the reference's queue order, as a pixel's nine
+    primaries are -- group=1 is the colour along one ray, group=9 over a
+    frame's camera rays the frame's pixel sums (scenes.queue_pack() packs
+    them).  Returns (colours float32 [n / group, 3], t float32 [n] -- the
+    root's distance, 1e7 on a miss --, id int32 [n] -- the root's primitive or
+    -1), and [rays, shadow rays, intersect calls, undefined-behaviour events]
+    as a fourth item if counters."""
+    if prims is None:
+        prims, nprims = scenes.queue_scene()
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    n = rays.shape[0]
+    col = np.empty((n // group if 1 <= group <= 64 else 0, 3), np.float32)
+    t = np.empty(n, np.float32)
+    ids = np.empty(n, np.int32)
+    cnt = (C.c_uint64 * 4)()
+    check(entry("rtq_trace")(C.addressof(prims), nprims, rays.ctypes.data, n, group, col.ctypes.data, t.ctypes.data,
+                             ids.ctypes.data, C.addressof(cnt) if counters else None))
+    return (col, t, ids, list(cnt)) if counters else (col, t, ids)
+
+
+def queue_trace_async(rays, d_prims, nprims, group=1, out=None, counters=None, stream=None):
+    """queue_trace on device memory (rtq_trace_async): `rays` a contiguous
+    float32 device tensor [n, 6], n a multiple of `group`; `d_prims` a
+    contiguous device tensor of any dtype holding at least nprims 96-byte
+    primitives or a raw device address.  out=(colours, t, id) takes the
+    caller's tensors (float32 [n / group, 3], float32 [n], int32 [n]; t and id
+    may be None, which leaves that output out); by default all three are
+    allocated.  counters: an int64 device tensor [4] accumulated into.
+    Asynchronous on `stream` (a torch stream or a raw handle; default: torch's
+    current stream), ordered with the level-pass frames as rtq_render_async
+    is; not for graph capture.  Returns (colours, t, id)."""
+    import torch
+    if not (rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 6
+            and rays.is_contiguous()):
+        raise ValueError("queue_trace_async: rays must be a contiguous float32 device tensor [n, 6]")
+    n = rays.shape[0]
+    if not (isinstance(group, int) and 1 <= group <= 64 and n % group == 0):
+        raise ValueError("queue_trace_async: group must be 1..64 and divide the number of rays")
+    nc = n // group
+    if hasattr(d_prims, "data_ptr"):
+        if not (d_prims.is_cuda and d_prims.is_contiguous()
+                and d_prims.numel() * d_prims.element_size() >= C.sizeof(QPrimitive) * max(int(nprims), 0)):
+            raise ValueError("queue_trace_async: d_prims must be a contiguous device tensor of at least "
+                             "96 x nprims bytes")
+        d_prims = d_prims.data_ptr()
+    if out is None:
+        col = torch.empty((nc, 3), dtype=torch.float32, device=rays.device)
+        t = torch.empty(n, dtype=torch.float32, device=rays.device)
+        ids = torch.empty(n, dtype=torch.int32, device=rays.device)
+    else:
+        col, t, ids = out
+        for x, dt, numel in ((col, torch.float32, 3 * nc), (t, torch.float32, n), (ids, torch.int32, n)):
+            if (x is None and x is not col) or (x is not None and x.is_cuda and x.dtype == dt and x.numel() >= numel
+                                                  and x.is_contiguous()):
+                continue
+            raise ValueError("queue_trace_async: out must hold contiguous device tensors: float32 [n / group, 3], "
+                             "float32 [n] or None, int32 [n] or None")
+    if counters is not None and not (counters.is_cuda and counters.dtype == torch.int64 and counters.numel() == 4
+                                     and counters.is_contiguous()):
+        raise ValueError("queue_trace_async: counters must be a contiguous int64 device tensor [4]")
+    if stream is None:
+        stream = torch.cuda.current_stream(rays.device)
+    stream = getattr(stream, "cuda_stream", stream)
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    if n:                                                  # (an empty tensor has no address to pass)
+        check(entry("rtq_trace_async")(d_prims, nprims, rays.data_ptr(), n, group, ptr(col), ptr(t), ptr(ids),
+                                       ptr(counters), stream))
+    return col, t, ids
 
 
 class SmallptFrame:

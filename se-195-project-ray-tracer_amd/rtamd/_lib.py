@@ -35,7 +35,7 @@ EXPORTS = ("rt_last_error", "rt_device_count", "rt_set_device", "rt_release", "r
            "spt_multi_read_frame", "spt_multi_counters", "spt_multi_band_buffers", "spt_render_multi",
            "spt_multi_cache_info", "rtq_render", "rtq_render_async",
            "rtw_prims_create", "rtq_prims_create", "rtp_scene_destroy", "rtw_prims_set_async", "rtq_prims_set_async",
-           "rtp_query_async", "rtw_trace_async", "rtw_trace")
+           "rtp_query_async", "rtw_trace_async", "rtw_trace", "rtq_trace_async", "rtq_trace")
 
 
 class RTError(RuntimeError):
@@ -181,6 +181,9 @@ def lib():
     if hasattr(L, "rtw_trace_async"):
         L.rtw_trace_async.argtypes = [vp, i, vp, C.c_size_t, i, vp, vp, vp, u64p, vp]
         L.rtw_trace.argtypes = [vp, i, vp, C.c_size_t, i, vp, vp, vp, u64p]
+    if hasattr(L, "rtq_trace_async"):
+        L.rtq_trace_async.argtypes = [vp, i, vp, C.c_size_t, i, vp, vp, vp, u64p, vp]
+        L.rtq_trace.argtypes = [vp, i, vp, C.c_size_t, i, vp, vp, vp, u64p]
     _lib = L
     return L
 

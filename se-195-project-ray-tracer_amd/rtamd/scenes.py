@@ -341,6 +341,53 @@ def whitted_pack(colors, ocl=False):
     return ((r | g | b) if ocl else ((r + g + b) & 0xffffffff)).astype(np.uint32)
 
 
+def queue_camera_rays(w, h, row_begin=0, row_end=None):
+    """The primary rays of the queue tracer's frame, as rtq_trace takes them:
+    float32 [row_end - row_begin, w, 9, 6] rows of (o.xyz, d.xyz), a pixel's
+    nine in the order the reference pushes them (tx outer, ty inner), so
+    group=9 makes each pixel one chain.  raytracer_non_OpenCL.c:299-339:
+    DX = (3 - -3) / w, DY = (-2.25 - 2.25) / h, SX = WX1 + x * DX,
+    SY = WY1 + y * DY, dir = (S + D * (t / 2)) - cam with dz = 0 - (-7),
+    scaled by 1 / sqrt(dir . dir); the eye is (0, 0.25, -7).  Float32
+    arithmetic, one operation per numpy call, in the reference's order."""
+    if row_end is None:
+        row_end = h
+    if row_begin < 0 or row_end > h or row_begin >= row_end:
+        raise ValueError("queue_camera_rays: rows must satisfy 0 <= row_begin < row_end <= h")
+    WX1, WY1 = f32(-3.0), f32(2.25)
+    DX = (f32(3.0) - WX1) / f32(w)
+    DY = (f32(-2.25) - WY1) / f32(h)
+    SX = WX1 + np.arange(w).astype(f32) * DX
+    SY = WY1 + np.arange(row_begin, row_end).astype(f32) * DY
+    out = np.empty((row_end - row_begin, w, 9, 6), f32)
+    out[..., 0], out[..., 1], out[..., 2] = f32(0.0), f32(0.25), f32(-7.0)
+    for sub in range(9):
+        tx, ty = f32(sub // 3 - 1), f32(sub % 3 - 1)
+        dx = (SX + DX * (tx / f32(2.0))) - f32(0.0)
+        dy = (SY + DY * (ty / f32(2.0))) - f32(0.25)
+        dx, dy = np.broadcast_arrays(dx[None, :], dy[:, None])
+        dz = f32(0.0) - f32(-7.0)
+        l = f32(1.0) / np.sqrt(dx * dx + dy * dy + dz * dz)
+        out[:, :, sub, 3], out[:, :, sub, 4], out[:, :, sub, 5] = dx * l, dy * l, dz * l
+    return out
+
+
+def queue_pack(colors):
+    """raytracer_non_kernel's pixel from its accumulator (:436-447): colors
+    float32 [..., 3] (rtq_trace's chain colours) -> uint32 [...].  x28
+    (256 / 9 in int), C's (int) conversion -- INT_MIN for a NaN or a value
+    outside int's range, as x86's cvttss2si gives -- clamped to 255 from above
+    only, each channel's low byte, packed r | g << 8 | b << 16 (uchar4
+    r, g, b, 0)."""
+    colors = np.asarray(colors, dtype=f32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = colors * f32(28.0)
+        ok = np.isfinite(v) & (v < f32(2147483648.0)) & (v >= f32(-2147483648.0))
+        c = np.where(ok, np.trunc(np.where(ok, v, f32(0.0))).astype(np.int64), np.int64(-2147483648))
+    c = np.minimum(c, 255) & 0xff
+    return (c[..., 0] | (c[..., 1] << 8) | (c[..., 2] << 16)).astype(np.uint32)
+
+
 def seeds(width, height, seed=1):
     """AllocateBuffers' seed fill (smallptGPU.cpp:105-110): srand(seed), then
     2*width*height glibc rand() words clamped to >= 2 (spt_seed_fill)."""
