@@ -325,8 +325,10 @@ int spt_scene_release_captures(const spt_scene *scene);
  * are those of a scene created from the edited array, bit for bit; the learnt
  * dispatch order and the work counters stay.  A tree refitted after large
  * changes, or many times, may walk slower than a fresh one (its splits and
- * its partition were chosen for the original spheres): spt_scene_create is the
- * remedy.
+ * its partition were chosen for the original spheres, and its leaves still
+ * hold the spheres they were dealt then): spt_scene_regroup_async re-deals the
+ * spheres into the tree on the device, stream-ordered; spt_scene_create
+ * remains the remedy for splits and a partition that no longer fit.
  *
  * The first update of a scene builds what a refit needs (the topology, once
  * more on the host; device metadata; staging) and is as slow as a create; a
@@ -347,6 +349,43 @@ int spt_scene_update_async(spt_scene *scene, const rt_sphere *spheres, unsigned 
  * the first update and for a scene without a hierarchy). */
 #define SPT_UPDATE_INFO_WORDS 5
 int spt_scene_update_info(const spt_scene *scene, uint64_t *out, int nout);
+/* Re-deals the current spheres of a prepared scene into the frozen shape of
+ * its hierarchy, on the device, and refits: top-down, the entries of every
+ * inner binary node's range are stable-sorted along the node's split axis by
+ * the total-order integer key of their centres (bits ^ (bits >> 31 ?
+ * 0xffffffff : 0x80000000); no float is compared, a NaN has its place), and
+ * the left child takes the lower part.  Frozen: the always / tree partition,
+ * every node's entry range and axis, the octant layouts and their links, the
+ * 8-wide slots and child words, the leaf size, the node counts, the LDS
+ * layout and the kernel family -- so no launch parameter changes, nothing is
+ * reallocated, graphs captured from this scene's launches stay valid and the
+ * learnt dispatch order stays.  Changed: which sphere sits at which tree
+ * position, and what follows from it (the entries' geometry, every box,
+ * margin and quantised child box, the 8-wide highest-index table).  Culling
+ * is exact, so frames, queries, radiance and pixel-list calls enqueued on
+ * `stream` before the call and after it give the same bits; the later ones
+ * walk tighter leaves.  When to regroup is the caller's decision (after an
+ * animation has carried the spheres away from where the tree was built).
+ *
+ * Device work is ordered on `stream` and nothing is synchronised.  The first
+ * regroup of a scene builds its metadata and scratch (and, for a scene never
+ * updated, what the first spt_scene_update_async builds, which
+ * spt_scene_update_info then reports); later calls allocate nothing.  A sort
+ * over more than 256 entries ranks by counting, quadratic in the range: fine
+ * for tens of thousands of spheres, not meant for millions.  A scene without a
+ * hierarchy returns RT_OK and launches nothing.
+ *
+ * RT_ERR_INVALID, with the scene untouched: a null scene, a capturing stream,
+ * another current device. */
+int spt_scene_regroup_async(spt_scene *scene, void *stream);
+/* Host bookkeeping of spt_scene_regroup_async, fills out[0 .. min(nout,
+ * SPT_REGROUP_INFO_WORDS)): [0] regroups run  [1] levels of the binary tree
+ * [2] levels sorted by passes of their own (those that hold a range above
+ * 256 entries; the rest is sorted in LDS, a subtree per block)  [3] bytes
+ * of regroup metadata and scratch on the device.  All 0 before the first
+ * regroup and for a scene without a hierarchy. */
+#define SPT_REGROUP_INFO_WORDS 4
+int spt_scene_regroup_info(const spt_scene *scene, uint64_t *out, int nout);
 /* Blocking (waits for the device), for tests and tools: the hierarchy as the
  * device holds it, five sections back to back in `out` -- the node records of
  * the eight octant layouts (two float4 each), the entries' geometry (float4:
@@ -636,6 +675,9 @@ int spt_multi_set_scene(spt_multi *m, const rt_sphere *spheres, unsigned nsphere
 /* spt_scene_update_async on every band's scene, each on its band's stream:
  * no band is re-prepared or waited for (but for the cases that call names). */
 int spt_multi_update_scene(spt_multi *m, const rt_sphere *spheres, unsigned first, unsigned count);
+/* spt_scene_regroup_async on every band's scene, each on its band's stream:
+ * no band is re-prepared or waited for. */
+int spt_multi_regroup_scene(spt_multi *m);
 /* Pixel-row bounds: rows[k] .. rows[k+1] hold band k's rows in FLIPPED
  * order, i.e. band k renders pixel rows [h - rows[k+1], h - rows[k]).
  * rows: ngpus + 1 ints. */

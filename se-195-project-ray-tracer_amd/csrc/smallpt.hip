@@ -1597,9 +1597,25 @@ __global__ void __launch_bounds__(256) list_dedup_kernel(const int *__restrict__
 #include <memory>
 #include "spt_bvh.h"
 #include "spt_refit.h"
+#include "spt_regroup.h"
 #include "spt_sched.h"
 
 using sptpolicy::Shape;
+
+// What spt_scene_regroup_async adds, built at the first regroup: the launch
+// plan (sptregroup::Plan), Topo's and the plan's ints on the device, and the
+// sort's scratch (a key and an id per tree entry).
+struct SceneRegroup {
+    sptregroup::Plan plan;
+    int *d_ints = nullptr;             // left | right | axis | wpos | sub | desc
+    uint32_t *d_scratch = nullptr;     // nb keys, then nb ids
+    uint64_t regroups = 0, bytes = 0;
+    ~SceneRegroup()
+    {
+        if (d_ints) (void)hipFree(d_ints);
+        if (d_scratch) (void)hipFree(d_scratch);
+    }
+};
 
 // What spt_scene_update_async keeps with a scene, built at the first update (a
 // scene that is never updated has none): the frozen topology of the hierarchy
@@ -1609,6 +1625,8 @@ using sptpolicy::Shape;
 struct SceneRefit {
     static constexpr int SLOTS = 2;
     sptrefit::Meta meta;
+    sptregroup::Topo topo;             // the children and axes beside meta (host only until a regroup)
+    std::unique_ptr<SceneRegroup> regroup;   // null until the first regroup
     int *d_meta = nullptr;             // range | pos | order | wslot
     float *d_scratch = nullptr;        // entry boxes (six planes of nb floats, padded to 16 B), then two float4 per node
     int *d_lights = nullptr;           // light indices, ascending (n ints)
@@ -2004,6 +2022,7 @@ int refit_prepare(spt_scene *sc)
             (sc->leaf_max ? wb.nnodes : 0) != sc->bvh.wnodes ||
             !sptrefit::build_meta(b, (int)always.size(), sc->leaf_max ? wb.words.data() : nullptr, wb.nnodes, m))
             return rtrt::fail(RT_ERR_INVALID, "spt_scene_update_async: the scene's topology cannot be rebuilt");
+        sptregroup::build_topo(b, m, r->topo);
         std::vector<int> ints;
         ints.reserve(m.ints());
         for (const std::vector<int> *v : {&m.range, &m.pos, &m.order, &m.wslot}) ints.insert(ints.end(), v->begin(), v->end());
@@ -2148,6 +2167,113 @@ extern "C" int spt_scene_update_info(const spt_scene *sc, uint64_t *out, int nou
     const uint64_t v[SPT_UPDATE_INFO_WORDS] = {r ? r->updates : 0, r ? r->refits : 0, r ? r->light_rebuilds : 0,
                                                r ? r->reallocs : 0, r ? r->meta_bytes : 0};
     std::copy(v, v + std::min(nout, (int)SPT_UPDATE_INFO_WORDS), out);
+    return RT_OK;
+}
+
+// ---- regroup (spt_regroup.h)
+namespace {
+
+// The first regroup of a scene: the launch plan, Topo's and the plan's ints on
+// the device, the sort's scratch.  RT_SPT_REGROUP_LDS=<entries>: the largest
+// subtree the LDS tier takes (A/B; 0: no LDS tier, every tree level sorted by
+// passes of its own; at most SUB_MAX).
+int regroup_prepare(spt_scene *sc)
+{
+    SceneRefit &r = *sc->refit;
+    std::unique_ptr<SceneRegroup> g(new SceneRegroup());
+    const char *le = getenv("RT_SPT_REGROUP_LDS");
+    const int sub_max = le ? std::min(std::max(atoi(le), 0), sptregroup::SUB_MAX) : sptregroup::SUB_DEFAULT;
+    sptregroup::build_plan(r.meta, r.topo, sub_max, g->plan);
+    std::vector<int> ints;
+    for (const std::vector<int> *v : {&r.topo.left, &r.topo.right, &r.topo.axis, &r.topo.wpos, &g->plan.sub, &g->plan.desc})
+        ints.insert(ints.end(), v->begin(), v->end());
+    hipError_t e = hipMalloc(&g->d_ints, sizeof(int) * ints.size());
+    if (e == hipSuccess) e = hipMalloc(&g->d_scratch, 2 * sizeof(uint32_t) * (size_t)r.meta.nb);
+    if (e == hipSuccess) e = hipMemcpy(g->d_ints, ints.data(), sizeof(int) * ints.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_regroup_async metadata upload");
+    g->bytes = sizeof(int) * ints.size() + 2 * sizeof(uint32_t) * (size_t)r.meta.nb;
+    r.regroup = std::move(g);
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int spt_scene_regroup_async(spt_scene *sc, void *stream)
+{
+    if (!sc) return rtrt::fail(RT_ERR_INVALID, "spt_scene_regroup_async: null scene");
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(s, &cap);
+    if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_regroup_async stream");
+    if (cap != hipStreamCaptureStatusNone)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_regroup_async: the stream is capturing");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != sc->device)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_regroup_async: the scene's device is not the current one");
+    if (!sc->bvh.node) return RT_OK;
+    int rc;
+    if (!sc->refit && (rc = refit_prepare(sc))) return rc;
+    SceneRefit &r = *sc->refit;
+    if (!r.regroup && (rc = regroup_prepare(sc))) return rc;
+    SceneRegroup &g = *r.regroup;
+    const sptregroup::Plan &p = g.plan;
+    const sptrefit::DevRefit v = refit_view(*sc);
+    const size_t nn = (size_t)v.nn;
+    sptregroup::DevRegroup d = {};
+    d.spheres = sc->d_spheres;
+    d.ids = const_cast<int *>(sc->bvh.id);
+    d.maxid = (uint32_t *)const_cast<uint4 *>(sc->bvh.wmax);
+    d.nb = v.nb;
+    d.range = v.range; d.order = v.order;
+    d.left = g.d_ints; d.right = d.left + nn; d.axis = d.right + nn; d.wpos = d.axis + nn;
+    d.n_small = v.n_small; d.n_wave = v.n_wave; d.n_block = v.n_block;
+    d.keys = g.d_scratch;
+    d.tmp = (int *)(g.d_scratch + v.nb);
+    const int2 *sub = (const int2 *)(d.wpos + nn), *desc = sub + p.sub.size() / 2;
+    // the levels above the LDS tier, top-down: keys, ranks, copy back
+    rc = RT_OK;
+    for (size_t l = 0; l < p.lev_count.size() && rc == RT_OK; l++) {
+        const dim3 grid(p.lev_count[l]), block(sptregroup::CHUNK);
+        hipLaunchKernelGGL(sptregroup::regroup_keys, grid, block, 0, s, d, desc + p.lev_first[l]);
+        hipLaunchKernelGGL(sptregroup::regroup_rank, grid, block, 0, s, d, desc + p.lev_first[l]);
+        hipLaunchKernelGGL(sptregroup::regroup_copy, grid, block, 0, s, d, desc + p.lev_first[l]);
+        rc = rtrt::check_launch("spt regroup level");
+    }
+    if (rc == RT_OK && !p.sub.empty()) {
+        hipLaunchKernelGGL(sptregroup::regroup_subtree, dim3(p.sub.size() / 2), dim3(256), 0, s, d, sub);
+        rc = rtrt::check_launch("spt regroup_subtree");
+    }
+    // ids is final: the whole scene's geo and entry boxes, the refit, the highest-index table
+    if (rc == RT_OK) {
+        hipLaunchKernelGGL(sptrefit::refit_gather, dim3((v.nb + v.na + 255) / 256), dim3(256), 0, s, v, 0, 0, 0, sc->n,
+                           (const int *)nullptr, 0, 0);
+        rc = rtrt::check_launch("spt refit_gather");
+    }
+    if (rc == RT_OK) {
+        const int b_small = (v.n_small + 31) / 32, b_wave = (v.n_wave + 3) / 4;
+        hipLaunchKernelGGL(sptrefit::refit_nodes, dim3(b_small + b_wave + v.n_block), dim3(256), 0, s, v, b_small, b_wave);
+        rc = rtrt::check_launch("spt refit_nodes");
+        if (rc == RT_OK && v.wwords) {
+            hipLaunchKernelGGL(sptrefit::refit_wide, dim3((8 * v.wn + 255) / 256), dim3(256), 0, s, v);
+            hipLaunchKernelGGL(sptregroup::regroup_maxid, dim3(b_small + b_wave + v.n_block), dim3(256), 0, s, d, b_small,
+                               b_wave);
+            rc = rtrt::check_launch("spt regroup_maxid");
+        }
+    }
+    if (rc == RT_OK) {
+        r.boxes_valid = true;
+        g.regroups++;
+    }
+    return rc;
+}
+
+extern "C" int spt_scene_regroup_info(const spt_scene *sc, uint64_t *out, int nout)
+{
+    if (!sc || !out || nout < 1) return rtrt::fail(RT_ERR_INVALID, "spt_scene_regroup_info: bad arguments");
+    const SceneRegroup *g = sc->refit ? sc->refit->regroup.get() : nullptr;
+    const uint64_t v[SPT_REGROUP_INFO_WORDS] = {g ? g->regroups : 0, g ? (uint64_t)g->plan.levels : 0,
+                                                g ? (uint64_t)g->plan.lev_count.size() : 0, g ? g->bytes : 0};
+    std::copy(v, v + std::min(nout, (int)SPT_REGROUP_INFO_WORDS), out);
     return RT_OK;
 }
 

@@ -245,6 +245,18 @@ extern "C" int spt_multi_update_scene(spt_multi *m, const rt_sphere *spheres, un
     return RT_OK;
 }
 
+extern "C" int spt_multi_regroup_scene(spt_multi *m)
+{
+    if (!m) return rtrt::fail(RT_ERR_INVALID, "spt_multi_regroup_scene: null pointer");
+    rtrt::DeviceScope scope;
+    for (Band &b : m->bands) {
+        int rc = scope.select(b.device);
+        if (rc == RT_OK) rc = spt_scene_regroup_async(b.scene, b.stream);
+        if (rc) return rc;
+    }
+    return RT_OK;
+}
+
 extern "C" int spt_multi_bands(const spt_multi *m, int *rows)
 {
     if (!m || !rows) return rtrt::fail(RT_ERR_INVALID, "spt_multi_bands: null pointer");

@@ -324,6 +324,28 @@ class SmallptScene:
         check(entry("spt_scene_update_info")(self.handle, out, len(out)))
         return dict(zip(self.UPDATE_INFO, (int(v) for v in out)))
 
+    def regroup(self, stream=None):
+        """Re-deals the scene's current spheres into the frozen shape of its
+        hierarchy on the device and refits (spt_scene_regroup_async):
+        asynchronous on `stream` (as update()), the frames keep their bits,
+        the walks get tighter leaves.  Nothing happens on a scene without a
+        hierarchy."""
+        if stream is None:
+            import sys
+            torch = sys.modules.get("torch")
+            stream = torch.cuda.current_stream() if torch is not None and torch.cuda.is_initialized() else None
+        stream = getattr(stream, "cuda_stream", stream)
+        check(entry("spt_scene_regroup_async")(self.handle, stream))
+
+    # spt_scene_regroup_info's words in order
+    REGROUP_INFO = ("regroups", "levels", "global_levels", "bytes")
+
+    def regroup_info(self):
+        """Host bookkeeping of regroup() (spt_scene_regroup_info): a dict keyed by REGROUP_INFO."""
+        out = (C.c_uint64 * len(self.REGROUP_INFO))()
+        check(entry("spt_scene_regroup_info")(self.handle, out, len(out)))
+        return dict(zip(self.REGROUP_INFO, (int(v) for v in out)))
+
     def hierarchy(self):
         """The hierarchy as the device holds it (spt_scene_read_hierarchy;
         waits for the device): "nodes" float32 [16 x binary nodes, 4] (the
@@ -590,6 +612,11 @@ class SmallptMulti:
         if count is None:
             count = len(spheres)
         check(entry("spt_multi_update_scene")(self.handle, C.cast(spheres, C.c_void_p), first, count))
+
+    def regroup_scene(self):
+        """SmallptScene.regroup on every band's scene, each on its band's
+        stream (spt_multi_regroup_scene)."""
+        check(entry("spt_multi_regroup_scene")(self.handle))
 
     def upload(self, seeds, colors=None):
         check(lib().spt_multi_upload(self.handle, colors.ctypes.data if colors is not None else None,

@@ -28,6 +28,7 @@ EXPORTS = ("rt_last_error", "rt_device_count", "rt_set_device", "rt_release", "r
            "spt_group_count", "spt_scene_render_list_async", "spt_groups_pack_async", "spt_groups_unpack_async",
            "spt_pack_pixels_async",
            "spt_scene_update_async", "spt_scene_update_info", "spt_scene_read_hierarchy", "spt_multi_update_scene",
+           "spt_scene_regroup_async", "spt_scene_regroup_info", "spt_multi_regroup_scene",
            "spt_scene_query_async", "spt_scene_radiance_async", "spt_scene_render_pixels_async",
            "spt_scene_render_pixels_stats_async", "spt_frame_plan_scratch_bytes", "spt_frame_plan_async",
            "spt_multi_create", "spt_multi_destroy", "spt_multi_set_scene", "spt_multi_bands", "spt_multi_upload",
@@ -137,6 +138,10 @@ def lib():
         L.spt_scene_update_info.argtypes = [vp, vp, i]
         L.spt_scene_read_hierarchy.argtypes = [vp, vp, C.c_size_t, vp]
         L.spt_multi_update_scene.argtypes = [vp, vp, u, u]
+    if hasattr(L, "spt_scene_regroup_async"):
+        L.spt_scene_regroup_async.argtypes = [vp, vp]
+        L.spt_scene_regroup_info.argtypes = [vp, vp, i]
+        L.spt_multi_regroup_scene.argtypes = [vp]
     if hasattr(L, "spt_scene_query_async"):
         L.spt_scene_query_async.argtypes = [vp, vp, vp, C.c_size_t, i, vp, vp, vp]
     if hasattr(L, "spt_scene_radiance_async"):

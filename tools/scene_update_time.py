@@ -10,7 +10,13 @@ scenes (n256, cloud(3000), BASELINE configs[4]'s 10k spheres, cloud(56000)):
   (c) one 640x480 4-spp frame on the scene refitted through all those steps
       against the same frame on a fresh scene of the same final array
       (tools/_spt.py's event loop; both after three warming launches, which
-      teach a hierarchy scene its dispatch order).
+      teach a hierarchy scene its dispatch order);
+  (d) regroup: spt_scene_regroup_async + stream idle on that refitted scene,
+      the host time of the call, the first regroup on its own, and the same
+      frame on the regrouped tree, placed between (c)'s two;
+  (e) the regroup with the LDS tier given subtrees of at most 0 (every tree
+      level sorted by passes of its own), 64, 256, 1024 and 4096 entries
+      (RT_SPT_REGROUP_LDS, a fresh scene of the final array) against (d).
 
 (a) and (b) are host clocks around work that ends in a synchronise; median of
 REPS (default 20) with min-max.  Writes the log to --out, default the next
@@ -32,6 +38,7 @@ import refit_check as rc  # noqa: E402
 import scenes_layouts as sl  # noqa: E402
 
 W, H, SPP = 640, 480, 4
+LDS_SIZES = (0, 64, 256, 1024, 4096)    # RT_SPT_REGROUP_LDS values of (e); 0: the per-level form
 
 
 def scenes():
@@ -63,6 +70,58 @@ def steps(rows, count):
 
 def stat(ts):
     return "%.3f ms (min %.3f, max %.3f)" % (float(np.median(ts)), min(ts), max(ts))
+
+
+def time_regroups(sc, st, warm, reps):
+    """(first call + idle, later calls + idle, their host times): the work of
+    a regroup does not depend on how the entries lie, so repeating it on the
+    regrouped tree times the same launches."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    sc.regroup(stream=st)
+    st.synchronize()
+    first = 1e3 * (time.perf_counter() - t0)
+    tg, th = [], []
+    for i in range(warm + reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sc.regroup(stream=st)
+        t1 = time.perf_counter()
+        st.synchronize()
+        t2 = time.perf_counter()
+        if i >= warm:
+            tg.append(1e3 * (t2 - t0))
+            th.append(1e3 * (t1 - t0))
+    return first, tg, th
+
+
+def regroup_lines(say, sc, fa, fb, last, n, st, warm, reps, rebuild, refit_frame, fresh_frame):
+    """(d) a regroup of the tree refitted through all the steps, and the frame
+    on it, between the refit-only frame and the fresh tree's; (e) the same
+    regroup with every level sorted by passes of its own (no LDS tier)."""
+    first, tg, th = time_regroups(sc, st, warm, reps)
+    ri = sc.regroup_info()
+    tq = _spt.event_ms(lambda: fa.render(SPP, stream=st), warm, reps, st)
+    same = fa.same_bits(fb)
+    say("  (d) regroup + idle          : %s   host time of the call: %s   first regroup: %.3f ms" % (
+        stat(tg), stat(th), first))
+    say("      %d tree levels, %d by global passes, %d regroup bytes; (a) / (d) = %.1f" % (
+        ri["levels"], ri["global_levels"], ri["bytes"], rebuild / float(np.median(tg))))
+    q = float(np.median(tq))
+    gap = refit_frame - fresh_frame
+    say("      frame, regrouped tree   : %s   refit-only %.3f, fresh %.3f: %s of the gap closed   same bits: %s" % (
+        stat(tq), refit_frame, fresh_frame, "%.0f %%" % (100 * (refit_frame - q) / gap) if gap > 0 else "n/a", same))
+    for sub_max in LDS_SIZES:
+        os.environ["RT_SPT_REGROUP_LDS"] = str(sub_max)
+        try:
+            flat = rtamd.SmallptScene(last, n)
+            first0, tg0, th0 = time_regroups(flat, st, warm, reps)
+        finally:
+            del os.environ["RT_SPT_REGROUP_LDS"]
+        ri0 = flat.regroup_info()
+        say("  (e) LDS tier up to %4d + idle: %s   host time of the call: %s   %d global levels   (e) / (d) = %.2f" % (
+            sub_max, stat(tg0), stat(th0), ri0["global_levels"], float(np.median(tg0)) / float(np.median(tg))))
+        flat.close()
 
 
 def main():
@@ -134,6 +193,9 @@ def main():
             float(np.median(ta)) / float(np.median(tb)), ui["refits"], ui["reallocations"]))
         say("  (c) frame, refitted tree    : %s   fresh tree: %s   ratio %.3f   same bits: %s" % (
             stat(tr), stat(tf), float(np.median(tr)) / float(np.median(tf)), same))
+        if info["nodes"]:
+            regroup_lines(say, sc, fa, fb, arrays[-1], n, st, warm, reps, float(np.median(ta)), float(np.median(tr)),
+                          float(np.median(tf)))
         sc.close()
         fresh.close()
     with open(out, "w") as f:
