@@ -212,10 +212,11 @@ def test_rejected_regroups_leave_the_scene(rt, world, monkeypatch):
 def test_graph_captured_before_a_regroup_replays_after_it(rt, world, monkeypatch):
     """No address and no launch parameter changes: the replay renders the
     oracle's frame of the edited scene over the regrouped tree.  (The scene's
-    hierarchy is not read back in here: with SmallptScene.hierarchy() called
-    before the capture and before the replay, the replay left the frame's
-    sentinels in place, while the same capture, regroup and replay without
-    the read-back render the right frame; not explained yet.)"""
+    hierarchy is not read back in here: a replay once left the frame's
+    sentinels in place with SmallptScene.hierarchy() called before the capture
+    and before the replay.  The read-back is not the trigger; what was
+    narrowed down is in DESIGN.md, section 3, "Captured graphs across scene
+    edits".)"""
     import torch
     su._clean(monkeypatch)
     S, n, rows = world[0]("cloud3000")
