@@ -349,6 +349,68 @@ int spt_scene_update_async(spt_scene *scene, const rt_sphere *spheres, unsigned 
  * the first update and for a scene without a hierarchy). */
 #define SPT_UPDATE_INFO_WORDS 5
 int spt_scene_update_info(const spt_scene *scene, uint64_t *out, int nout);
+
+/* Moves spheres [first, first + count) of a prepared scene from DEVICE memory:
+ * d_geom holds four floats per sphere (p.x, p.y, p.z, rad; sphere first + i
+ * takes entry i), on the scene's device, 16-byte aligned.  Only the centre and
+ * the radius change.  Emission, colour and refl stay, and with them the light
+ * list and the light count, the no-refraction flag, the kernel family, every
+ * launch parameter and every address: the host derives nothing, so the call
+ * copies nothing to or from the host, stages nothing, allocates nothing and
+ * synchronises nothing once the scene is prepared (below).  Any floats, under
+ * spt_scene_create's contract: the radius counts through rad * rad, a sphere
+ * with a non-finite centre or radius is never hit, boxes are taken from
+ * |rad|, and a sphere whose float box is not finite widens no box.
+ *
+ * After a move the scene is, bit for bit, the scene spt_scene_update_async
+ * leaves from the same edited spheres: the AoS array, the SoA geometry, the
+ * light record of a moved emitter and, for a hierarchy scene, the entries'
+ * geometry and boxes and the refit of every node, margin and 8-wide child box
+ * (three launches: a gather that reads d_geom, then the update's two refit
+ * kernels).  d_geom is read by the call's own kernels only: the caller may
+ * overwrite it in stream order right after the call.  Launches on `stream`
+ * enqueued before the call see the old scene, launches after it the new one.
+ * The library's host copy of the spheres does not follow a move;
+ * spt_scene_read_spheres reads the current ones.
+ *
+ * spt_scene_move_prepare builds what a move relies on -- what the first
+ * update builds (topology, device metadata), the light index array on the
+ * device, and entry boxes that hold the whole scene (one whole-scene refit on
+ * `stream`) -- or whichever of these an earlier update or regroup left
+ * missing.  It may allocate and it waits for `stream`.  An uncaptured move of
+ * an unprepared scene prepares it first.
+ *
+ * Capture: on a capturing stream a prepared scene's move is recorded (fixed
+ * kernels, every argument by value); each replay moves the spheres to what
+ * d_geom holds at that replay.  An unprepared scene fails RT_ERR_INVALID
+ * there.  As for captured launches of the scene, an spt_scene_update_async
+ * that later changes the light count or reallocates the light records leaves a
+ * recorded move stale: capture again.  Covered by the tests: a graph of a
+ * move and a render of a scene WITHOUT a hierarchy (fewer than 256 spheres);
+ * a graph of a hierarchy scene's move alone, the frames after its replays
+ * being ordinary launches.  Not covered, and to be avoided: replaying a
+ * captured render of a hierarchy scene with an edit of any kind (update,
+ * regroup, move) between capture and replay or recorded in the same graph --
+ * such replays have skipped work and hung ("Captured
+ * graphs across scene edits").
+ *
+ * RT_ERR_INVALID, with the scene untouched: a null scene or d_geom, a d_geom
+ * that is not 16-byte aligned, a range out of bounds, another current device,
+ * a capturing stream on an unprepared scene (move) or at all (prepare).
+ * count == 0 returns RT_OK and launches nothing. */
+int spt_scene_move_prepare(spt_scene *scene, void *stream);
+int spt_scene_move_async(spt_scene *scene, const float *d_geom, unsigned first, unsigned count, void *stream);
+/* Host bookkeeping of spt_scene_move_async, fills out[0 .. min(nout,
+ * SPT_MOVE_INFO_WORDS)): [0] moves enqueued (count > 0)  [1] those recorded on
+ * a capturing stream  [2] hierarchy refits they launched (the prepare's
+ * whole-scene refit is not one).  Replays of a recorded move are not counted. */
+#define SPT_MOVE_INFO_WORDS 3
+int spt_scene_move_info(const spt_scene *scene, uint64_t *out, int nout);
+/* Blocking (waits for the device), for tests and tools: the scene's spheres as
+ * the device holds them, scene-many records into out[0 .. cap).  A `cap` below
+ * the sphere count fails RT_ERR_INVALID. */
+int spt_scene_read_spheres(const spt_scene *scene, rt_sphere *out, unsigned cap);
+
 /* Re-deals the current spheres of a prepared scene into the frozen shape of
  * its hierarchy, on the device, and refits: top-down, the entries of every
  * inner binary node's range are stable-sorted along the node's split axis by

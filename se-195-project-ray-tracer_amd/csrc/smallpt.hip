@@ -1597,6 +1597,7 @@ __global__ void __launch_bounds__(256) list_dedup_kernel(const int *__restrict__
 #include <memory>
 #include "spt_bvh.h"
 #include "spt_refit.h"
+#include "spt_move.h"
 #include "spt_regroup.h"
 #include "spt_sched.h"
 
@@ -1636,7 +1637,9 @@ struct SceneRefit {
     int next = 0;
     int light_cap = 1;                 // light records d_soa has room for
     bool boxes_valid = false;          // the entry boxes hold the whole scene (after the first refit)
+    bool lights_valid = false;         // d_lights holds the light list (an update that touched an emitter, or move_prepare)
     uint64_t updates = 0, refits = 0, light_rebuilds = 0, reallocs = 0, meta_bytes = 0;
+    uint64_t moves = 0, moves_captured = 0, move_refits = 0;   // spt_scene_move_async's (spt_scene_move_info)
     ~SceneRefit()
     {
         if (d_meta) (void)hipFree(d_meta);
@@ -1660,6 +1663,16 @@ struct spt_scene {
     int nlights = 0;
     void *d_bvh = nullptr;            // nodes | geo | id | always geo | always id | wide nodes (large scenes)
     rt::smallpt::BvhView bvh = {};
+    // The spheres as the host last gave them (spt_scene_create, then every
+    // spt_scene_update_async).  After a spt_scene_move_async the centres and
+    // radii of the moved spheres are stale here -- the device's AoS array is
+    // the scene (spt_scene_read_spheres) -- while e, c and refl stay exact:
+    // only the host edits them.  Readers: refit_prepare runs the builders on
+    // it, and runs before the first move is enqueued (a move prepares the
+    // scene first), while this still is the scene as created; the update's
+    // light list and no_refr read e and refl alone.  Nothing else reads it
+    // (the scene caches of spt_render_async and spt_render_multi compare the
+    // caller's array with copies of their own, and their scenes are never moved).
     std::vector<rt_sphere> host;
     bool force_global = false;        // RT_SPT_GEO=global: scalar-load path at any size (A/B)
     mutable sptsched::SptSched sched;       // adaptive group order (hierarchy scenes)
@@ -1670,7 +1683,7 @@ struct spt_scene {
     // The most recent launch (written on the host by launch(), read by spt_scene_info).
     struct LastLaunch { int count = 0, wpb = 0, nblocks = 0, cg = 0, n1 = 0, n2 = 0, dual = 0, lds = 0; };
     mutable LastLaunch last;
-    std::unique_ptr<SceneRefit> refit; // spt_scene_update_async's state (null until the first update)
+    std::unique_ptr<SceneRefit> refit; // the edits' state (null until the first update, regroup or move_prepare)
 };
 
 namespace {
@@ -2062,6 +2075,58 @@ sptrefit::DevRefit refit_view(const spt_scene &sc)
     return v;
 }
 
+// refit_nodes and (8-wide scenes) refit_wide behind a gather on `s`.
+int launch_refit_tree(const sptrefit::DevRefit &v, hipStream_t s)
+{
+    const int b_small = (v.n_small + 31) / 32, b_wave = (v.n_wave + 3) / 4;
+    hipLaunchKernelGGL(sptrefit::refit_nodes, dim3(b_small + b_wave + v.n_block), dim3(256), 0, s, v, b_small, b_wave);
+    int rc = rtrt::check_launch("spt refit_nodes");
+    if (rc == RT_OK && v.wwords) {
+        hipLaunchKernelGGL(sptrefit::refit_wide, dim3((8 * v.wn + 255) / 256), dim3(256), 0, s, v);
+        rc = rtrt::check_launch("spt refit_wide");
+    }
+    return rc;
+}
+
+// What a move needs of a scene beyond refit_prepare: the light index array on
+// the device, and entry boxes that hold the whole scene.
+bool move_ready(const spt_scene &sc)
+{
+    return sc.refit && sc.refit->lights_valid && (!sc.bvh.node || sc.refit->boxes_valid);
+}
+
+// Builds the parts of that which are missing (spt_scene_move_prepare; not on a
+// capturing stream).  Allocates and waits for `s`.
+int move_prepare(spt_scene *sc, hipStream_t s, const char *who)
+{
+    int rc;
+    if (!sc->refit && (rc = refit_prepare(sc))) return rc;
+    SceneRefit &r = *sc->refit;
+    if (!r.lights_valid) {
+        // e is the host's alone to edit: sc->host names the emitters whatever moved
+        std::vector<int> lights;
+        for (int i = 0; i < sc->n; i++)
+            if (is_emitter(sc->host[i])) lights.push_back(i);
+        hipError_t e = hipSuccess;
+        if (!lights.empty())
+            e = hipMemcpyAsync(r.d_lights, lights.data(), sizeof(int) * lights.size(), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);    // (`lights` is pageable and ends with this scope)
+        if (e != hipSuccess) return rtrt::fail_hip(e, who);
+        r.lights_valid = true;
+    }
+    if (sc->bvh.node && !r.boxes_valid) {
+        // the whole scene's entry boxes (and geo) from the AoS array, as a regroup's refit takes them
+        const sptrefit::DevRefit v = refit_view(*sc);
+        hipLaunchKernelGGL(sptrefit::refit_gather, dim3((v.nb + v.na + 255) / 256), dim3(256), 0, s, v, 0, 0, 0, sc->n,
+                           (const int *)nullptr, 0, 0);
+        rc = rtrt::check_launch("spt refit_gather");
+        if (rc == RT_OK) rc = launch_refit_tree(v, s);
+        if (rc != RT_OK) return rc;
+        r.boxes_valid = true;
+    }
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" int spt_scene_update_async(spt_scene *sc, const rt_sphere *spheres, unsigned first, unsigned count,
@@ -2127,6 +2192,7 @@ extern "C" int spt_scene_update_async(spt_scene *sc, const rt_sphere *spheres, u
     if (e == hipSuccess && lights_touched && nl)
         e = hipMemcpyAsync(r.d_lights, h_lights, sizeof(int) * (size_t)nl, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_update_async copy");
+    if (lights_touched) r.lights_valid = true;           // (no light left: nothing reads the array)
     const sptrefit::DevRefit v = refit_view(*sc);
     const bool tree = v.nodes != nullptr;
     const int nrec = lights_touched ? std::max(1, nl) : 0;
@@ -2137,13 +2203,7 @@ extern "C" int spt_scene_update_async(spt_scene *sc, const rt_sphere *spheres, u
                        efirst, ecount, r.d_lights, nl, nrec);
     rc = rtrt::check_launch("spt refit_gather");
     if (rc == RT_OK && tree) {
-        const int b_small = (v.n_small + 31) / 32, b_wave = (v.n_wave + 3) / 4;
-        hipLaunchKernelGGL(sptrefit::refit_nodes, dim3(b_small + b_wave + v.n_block), dim3(256), 0, s, v, b_small, b_wave);
-        rc = rtrt::check_launch("spt refit_nodes");
-        if (rc == RT_OK && v.wwords) {
-            hipLaunchKernelGGL(sptrefit::refit_wide, dim3((8 * v.wn + 255) / 256), dim3(256), 0, s, v);
-            rc = rtrt::check_launch("spt refit_wide");
-        }
+        rc = launch_refit_tree(v, s);
         if (rc == RT_OK) {
             r.boxes_valid = true;
             r.refits++;
@@ -2167,6 +2227,83 @@ extern "C" int spt_scene_update_info(const spt_scene *sc, uint64_t *out, int nou
     const uint64_t v[SPT_UPDATE_INFO_WORDS] = {r ? r->updates : 0, r ? r->refits : 0, r ? r->light_rebuilds : 0,
                                                r ? r->reallocs : 0, r ? r->meta_bytes : 0};
     std::copy(v, v + std::min(nout, (int)SPT_UPDATE_INFO_WORDS), out);
+    return RT_OK;
+}
+
+// ---- geometry from device memory (spt_move.h)
+extern "C" int spt_scene_move_prepare(spt_scene *sc, void *stream)
+{
+    if (!sc) return rtrt::fail(RT_ERR_INVALID, "spt_scene_move_prepare: null scene");
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(s, &cap);
+    if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_move_prepare stream");
+    if (cap != hipStreamCaptureStatusNone)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_move_prepare: the stream is capturing");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != sc->device)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_move_prepare: the scene's device is not the current one");
+    return move_prepare(sc, s, "spt_scene_move_prepare light indices");
+}
+
+extern "C" int spt_scene_move_async(spt_scene *sc, const float *d_geom, unsigned first, unsigned count, void *stream)
+{
+    if (!sc || !d_geom) return rtrt::fail(RT_ERR_INVALID, "spt_scene_move_async: null pointer");
+    if ((uintptr_t)d_geom & 15) return rtrt::fail(RT_ERR_INVALID, "spt_scene_move_async: d_geom is not 16-byte aligned");
+    if (first > (unsigned)sc->n || count > (unsigned)sc->n - first)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_move_async: range out of bounds");
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(s, &cap);
+    if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_move_async stream");
+    const bool capturing = cap != hipStreamCaptureStatusNone;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != sc->device)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_move_async: the scene's device is not the current one");
+    if (capturing && !move_ready(*sc))
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_move_async: capture needs spt_scene_move_prepare first");
+    if (count == 0) return RT_OK;
+    int rc;
+    if (!move_ready(*sc) && (rc = move_prepare(sc, s, "spt_scene_move_async light indices"))) return rc;
+    SceneRefit &r = *sc->refit;
+    // Everything below is by value and fixed while the light list stays: a
+    // capture records exactly these launches.
+    const sptrefit::DevRefit v = refit_view(*sc);
+    const bool tree = v.nodes != nullptr;
+    const int lanes = std::max({(int)count, tree ? v.nb + v.na : 0, sc->nlights});
+    hipLaunchKernelGGL(sptrefit::move_gather, dim3((lanes + 255) / 256), dim3(256), 0, s, v, (const float4 *)d_geom,
+                       (int)first, (int)count, r.d_lights, sc->nlights);
+    rc = rtrt::check_launch("spt move_gather");
+    if (rc == RT_OK && tree) {
+        rc = launch_refit_tree(v, s);
+        if (rc == RT_OK) r.move_refits++;
+    }
+    if (rc == RT_OK) {
+        r.moves++;
+        if (capturing) r.moves_captured++;
+    }
+    return rc;
+}
+
+extern "C" int spt_scene_move_info(const spt_scene *sc, uint64_t *out, int nout)
+{
+    if (!sc || !out || nout < 1) return rtrt::fail(RT_ERR_INVALID, "spt_scene_move_info: bad arguments");
+    const SceneRefit *r = sc->refit.get();
+    const uint64_t v[SPT_MOVE_INFO_WORDS] = {r ? r->moves : 0, r ? r->moves_captured : 0, r ? r->move_refits : 0};
+    std::copy(v, v + std::min(nout, (int)SPT_MOVE_INFO_WORDS), out);
+    return RT_OK;
+}
+
+extern "C" int spt_scene_read_spheres(const spt_scene *sc, rt_sphere *out, unsigned cap)
+{
+    if (!sc || !out) return rtrt::fail(RT_ERR_INVALID, "spt_scene_read_spheres: null pointer");
+    if (cap < (unsigned)sc->n) return rtrt::fail(RT_ERR_INVALID, "spt_scene_read_spheres: buffer too small");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != sc->device)
+        return rtrt::fail(RT_ERR_INVALID, "spt_scene_read_spheres: the scene's device is not the current one");
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, sc->d_spheres, sizeof(rt_sphere) * (size_t)sc->n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return rtrt::fail_hip(e, "spt_scene_read_spheres");
     return RT_OK;
 }
 

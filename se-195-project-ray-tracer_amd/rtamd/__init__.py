@@ -307,13 +307,8 @@ class SmallptScene:
         array's length."""
         if count is None:
             count = len(spheres)
-        if stream is None:
-            import sys
-            torch = sys.modules.get("torch")
-            stream = torch.cuda.current_stream() if torch is not None and torch.cuda.is_initialized() else None
-        stream = getattr(stream, "cuda_stream", stream)
         ptr = None if spheres is None else C.cast(spheres, C.c_void_p)
-        check(entry("spt_scene_update_async")(self.handle, ptr, first, count, stream))
+        check(entry("spt_scene_update_async")(self.handle, ptr, first, count, self._stream(stream)))
 
     # spt_scene_update_info's words in order
     UPDATE_INFO = ("updates", "refits", "light_rebuilds", "reallocations", "metadata_bytes")
@@ -330,12 +325,7 @@ class SmallptScene:
         asynchronous on `stream` (as update()), the frames keep their bits,
         the walks get tighter leaves.  Nothing happens on a scene without a
         hierarchy."""
-        if stream is None:
-            import sys
-            torch = sys.modules.get("torch")
-            stream = torch.cuda.current_stream() if torch is not None and torch.cuda.is_initialized() else None
-        stream = getattr(stream, "cuda_stream", stream)
-        check(entry("spt_scene_regroup_async")(self.handle, stream))
+        check(entry("spt_scene_regroup_async")(self.handle, self._stream(stream)))
 
     # spt_scene_regroup_info's words in order
     REGROUP_INFO = ("regroups", "levels", "global_levels", "bytes")
@@ -345,6 +335,56 @@ class SmallptScene:
         out = (C.c_uint64 * len(self.REGROUP_INFO))()
         check(entry("spt_scene_regroup_info")(self.handle, out, len(out)))
         return dict(zip(self.REGROUP_INFO, (int(v) for v in out)))
+
+    @staticmethod
+    def _stream(stream):
+        """`stream` as a raw handle; None: torch's current stream where torch is in use, else the null stream."""
+        if stream is None:
+            import sys
+            torch = sys.modules.get("torch")
+            stream = torch.cuda.current_stream() if torch is not None and torch.cuda.is_initialized() else None
+        return getattr(stream, "cuda_stream", stream)
+
+    def move(self, geom, first=0, stream=None):
+        """Moves spheres [first, first + count) to the centres and radii in
+        `geom` (spt_scene_move_async): a contiguous float32 device tensor
+        [count, 4] of p.x, p.y, p.z, rad, 16-byte aligned, on the scene's
+        device.  Emission, colour and refl stay.  Asynchronous on `stream` (as
+        update()); nothing is copied to or from the host and `geom` may be
+        overwritten in stream order right after the call.  On a capturing
+        stream the move is recorded (move_prepare() first); a replay reads what
+        `geom` holds then."""
+        import torch
+        if not (isinstance(geom, torch.Tensor) and geom.is_cuda and geom.dtype == torch.float32 and geom.dim() == 2
+                and geom.shape[1] == 4 and geom.is_contiguous()):
+            raise ValueError("move: geom must be a contiguous float32 device tensor [count, 4]")
+        if geom.shape[0] == 0:                                 # (an empty tensor has no address to pass)
+            return
+        check(entry("spt_scene_move_async")(self.handle, geom.data_ptr(), first, geom.shape[0], self._stream(stream)))
+
+    def move_prepare(self, stream=None):
+        """Builds what move() relies on (spt_scene_move_prepare): the refit
+        metadata, the light indices on the device, one whole-scene refit on
+        `stream`.  Allocates and waits for `stream`; needed before a move is
+        captured, optional otherwise (the first uncaptured move does it)."""
+        check(entry("spt_scene_move_prepare")(self.handle, self._stream(stream)))
+
+    # spt_scene_move_info's words in order
+    MOVE_INFO = ("moves", "captured", "refits")
+
+    def move_info(self):
+        """Host bookkeeping of move() (spt_scene_move_info): a dict keyed by MOVE_INFO."""
+        out = (C.c_uint64 * len(self.MOVE_INFO))()
+        check(entry("spt_scene_move_info")(self.handle, out, len(out)))
+        return dict(zip(self.MOVE_INFO, (int(v) for v in out)))
+
+    def spheres(self):
+        """The spheres as the device holds them (spt_scene_read_spheres; waits
+        for the device): float32 [n, 11] rows of rad, p, e, c and refl as raw
+        bits -- Sphere's layout."""
+        rows = np.zeros((self.n, 11), np.float32)
+        check(entry("spt_scene_read_spheres")(self.handle, rows.ctypes.data, self.n))
+        return rows
 
     def hierarchy(self):
         """The hierarchy as the device holds it (spt_scene_read_hierarchy;

@@ -29,6 +29,7 @@ EXPORTS = ("rt_last_error", "rt_device_count", "rt_set_device", "rt_release", "r
            "spt_pack_pixels_async",
            "spt_scene_update_async", "spt_scene_update_info", "spt_scene_read_hierarchy", "spt_multi_update_scene",
            "spt_scene_regroup_async", "spt_scene_regroup_info", "spt_multi_regroup_scene",
+           "spt_scene_move_prepare", "spt_scene_move_async", "spt_scene_move_info", "spt_scene_read_spheres",
            "spt_scene_query_async", "spt_scene_radiance_async", "spt_scene_render_pixels_async",
            "spt_scene_render_pixels_stats_async", "spt_frame_plan_scratch_bytes", "spt_frame_plan_async",
            "spt_multi_create", "spt_multi_destroy", "spt_multi_set_scene", "spt_multi_bands", "spt_multi_upload",
@@ -142,6 +143,11 @@ def lib():
         L.spt_scene_regroup_async.argtypes = [vp, vp]
         L.spt_scene_regroup_info.argtypes = [vp, vp, i]
         L.spt_multi_regroup_scene.argtypes = [vp]
+    if hasattr(L, "spt_scene_move_async"):
+        L.spt_scene_move_prepare.argtypes = [vp, vp]
+        L.spt_scene_move_async.argtypes = [vp, vp, u, u, vp]
+        L.spt_scene_move_info.argtypes = [vp, vp, i]
+        L.spt_scene_read_spheres.argtypes = [vp, vp, u]
     if hasattr(L, "spt_scene_query_async"):
         L.spt_scene_query_async.argtypes = [vp, vp, vp, C.c_size_t, i, vp, vp, vp]
     if hasattr(L, "spt_scene_radiance_async"):
